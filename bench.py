@@ -13,8 +13,16 @@ whole-job rate (global pairs / max-over-ranks step time).  Strong scaling: ``--g
 holds the job's batch at B (``train_ioi.py``'s 256) and splits it over the ranks.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full               # + held-out IIA / accuracy
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + DIR/<name>.npy (seeded replay)
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8
     python bench.py --gpus 8          # no launcher: bench.py starts the 8 ranks itself (torch.distributed.run)
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line; ``--full`` adds the held-out
+IIA / accuracy evaluation.  ``--dump-outputs DIR`` then writes, as float64 ``DIR/train_*_loss.npy``, the losses the
+timed path returns from two more steps that start from the seeded start state (see ``dump_outputs``): they repeat
+from run to run to rounding, which the state after the timed steps does not, and they do not depend on ``--steps`` or
+``--warmup``.  The timed loop and the result line are the same with and without the option.
 
 ``--gpus N`` is binding: without a launcher environment and N > 1 the script launches N fresh rank
 processes (the parent makes no GPU call first and only relays their output); under a launcher whose
@@ -50,6 +58,12 @@ def parse():
     ap.add_argument("--graphs", type=int, default=int(os.environ.get("IIT_GRAPHS", "1")),
                     help="capture each train-step phase as a HIP graph (default on; 0 = eager)")
     ap.add_argument("--profile-dir", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also evaluate IIA / accuracy on held-out pairs after the timed steps (val_IIA, val_accuracy "
+                         "in the result line); a plain run only sets up, warms up, times and reports")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps run the timed path twice more from the seeded start state and write "
+                         "the losses it returns as DIR/<name>.npy (they repeat from run to run to rounding)")
     return ap.parse_args()
 
 
@@ -116,6 +130,40 @@ def setup(args, dev):
 REFERENCE_EAGER_PAIRS_PER_S = 1663.5
 
 
+DUMP_STEPS = 2  # steps replayed from the start state for --dump-outputs
+
+
+def dump_outputs(out_dir: str, start, step_fn, loss_fn, opt, train_set, batch: int, rank: int) -> None:
+    """``--dump-outputs``: after the timed steps (and off the clock) the timed path runs ``DUMP_STEPS`` more steps, from
+    the seeded start state ``start`` on the seeded first batches, and what a caller receives from them -- the losses
+    each returns -- is written as float64 ``DIR/<name>.npy``, one element per step.
+
+    Why not the state the timed steps ended in: the engine's fp32 atomics sum in arrival order (embedding / LayerNorm /
+    bias gradients, the gradient norm, split-K tiles), so a step repeats to rounding only, and the ~90 Adam steps of a
+    run (graph priming, warm-up, timed steps) amplify that to 6e-2 in a loss between two runs of one build.  From the
+    start state the first replayed step's IIT loss is a forward pass of the seeded weights; its strict and behaviour
+    losses follow that step's first and second clip + Adam update, and every loss of the second step follows a whole
+    step's forwards, backwards, clips and Adam updates (9.67 against 11.03 for the IIT loss), so a change in backward
+    or optimizer numerics moves them.  Measured on an MI355X, repeats agree within 4e-5 relative.  (Parameters and
+    per-tensor gradient norms are not dumped: an Adam update from zero moments is ``lr * sign(g)``, so last-bit noise
+    in a near-zero gradient moves a parameter by 2 * lr, and the norms of near-zero gradients vary by tens of
+    percent.)"""
+    import contextlib
+    start.restore()
+    loader = iter(train_set.make_loader(batch, 0))  # (the restored torch RNG gives the run's first epoch order)
+    ctx = step_fn.stream_context() if hasattr(step_fn, "stream_context") else contextlib.nullcontext()
+    outs = []
+    with ctx:
+        for _ in range(DUMP_STEPS):
+            base, abl = next(loader)
+            outs.append({k: float(v) for k, v in step_fn(base, abl, loss_fn, opt).items()})
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for k in outs[0]:
+            np.save(os.path.join(out_dir, k.replace("/", "_") + ".npy"),
+                    np.array([o[k] for o in outs], dtype=np.float64))
+
+
 def _free_port() -> int:
     import socket
     s = socket.socket()
@@ -142,6 +190,9 @@ def main():
     if args.gpus < 1:
         print(f"[bench] --gpus must be >= 1 (got {args.gpus})", file=sys.stderr)
         sys.exit(3)
+    if args.steps < 1:
+        print(f"[bench] --steps must be >= 1 (got {args.steps})", file=sys.stderr)
+        sys.exit(3)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
     from iit_amd.parallel import dist as pdist
@@ -165,6 +216,10 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
 
     pair, opt, loss_fn, it, step_fn, train_set, test_set = setup(args, dev)
+    start = None
+    if args.dump_outputs:
+        from iit_amd.engine.graphs import TrainStateSnapshot
+        start = TrainStateSnapshot(pair, opt)  # the seeded start state: dump_outputs replays from it after the timing
 
     import contextlib
     # the whole loop runs on the graph runner's stream (batches included): no per-step stream handoff
@@ -201,15 +256,19 @@ def main():
     global_batch = args.batch * world
     value = global_batch * args.steps / dt
 
-    # IIA / accuracy on held-out pairs (outside the timed region)
-    metrics = pair.make_test_metrics()
-    with torch.no_grad():
-        for i, (base, abl) in enumerate(test_set.make_loader(args.batch, 0)):
-            metrics.update(pair.run_eval_step(base, abl, loss_fn))
-            if i >= 3:
-                break
-    vals = metrics.to_dict()
     train_loss = {k: float(v) for k, v in out.items()} if isinstance(out, dict) else {}
+    vals = None
+    if args.full:
+        # IIA / accuracy on held-out pairs (outside the timed region)
+        metrics = pair.make_test_metrics()
+        with torch.no_grad():
+            for i, (base, abl) in enumerate(test_set.make_loader(args.batch, 0)):
+                metrics.update(pair.run_eval_step(base, abl, loss_fn))
+                if i >= 3:
+                    break
+        vals = metrics.to_dict()
+    if args.dump_outputs:  # last: it leaves the model DUMP_STEPS steps from the start state
+        dump_outputs(args.dump_outputs, start, step_fn, loss_fn, opt, train_set, args.batch, rank)
 
     if rank == 0:
         rec = {
@@ -235,10 +294,10 @@ def main():
                        "global_batch": global_batch, "seq_len": int(train_set.base_data.dataset.prompts.shape[1] - 1),
                        "parallelism": f"dp{world}", "engine": args.engine,
                        "graphs": bool(getattr(step_fn, "enabled", False))},
-            "val_IIA": round(float(vals["val/IIA"]), 3),
-            "val_accuracy": round(float(vals["val/accuracy"]), 3),
             "last_train_losses": {k: round(v, 4) for k, v in train_loss.items()},
         }
+        if vals is not None:  # --full
+            rec.update(val_IIA=round(float(vals["val/IIA"]), 3), val_accuracy=round(float(vals["val/accuracy"]), 3))
         print(json.dumps(rec))
         if os.environ.get("IIT_GEMM_REPORT"):
             from iit_amd.ops import gemm_dispatch

@@ -221,6 +221,27 @@ class _TrainState:
             self.ll.mark_weights_changed()
 
 
+class TrainStateSnapshot(_TrainState):
+    """A training state to return to later in the run (``bench.py --dump-outputs``): :class:`_TrainState` plus the
+    pair's node-sampling RNG.  It may be taken before the first forward, which is what first makes the flat arena's
+    bf16 mirror: ``restore`` re-derives the mirror from the restored fp32 weights, so captured graphs replay on them."""
+
+    def __init__(self, pair, optimizer):
+        import copy
+        super().__init__(pair, optimizer)
+        self.pair = pair
+        self.pair_rng = copy.deepcopy(getattr(pair, "rng", None))
+
+    @torch.no_grad()
+    def restore(self) -> None:
+        import copy
+        super().restore()
+        if self.flat is not None:
+            self.flat.refresh_shadow()
+        if self.pair_rng is not None:
+            self.pair.rng = copy.deepcopy(self.pair_rng)
+
+
 class GraphedTrainStep:
     def __init__(self, pair, optimizer=None, loss_fn=None, warmup: int = 1, enabled: Optional[bool] = None):
         self.pair = pair

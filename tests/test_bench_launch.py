@@ -75,6 +75,45 @@ def test_bench_world_mismatch_fails(tmp_path):
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
 
 
+def _run_bench(tmp_path, *args):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + list(args)
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=_bench_env(), cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-3000:]
+    return _json_line(out.stdout)
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run reports the timed steps only; the held-out evaluation (``val_IIA`` / ``val_accuracy``) is behind
+    ``--full``; ``--dump-outputs`` leaves the result line alone and writes the losses of two steps replayed from the
+    seeded start state, which therefore do not depend on how many steps trained before (they would without the
+    restore: after 3 + 1 steps the same two batches give other losses)."""
+    import numpy as np
+    plain = _run_bench(tmp_path, "--steps", "1", "--warmup", "0")
+    assert plain["steps"] == 1 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert plain["value"] == pytest.approx(plain["config"]["global_batch"] / plain["ms_per_step"] * 1e3, rel=1e-3)
+    assert "val_IIA" not in plain and "val_accuracy" not in plain
+    assert not [f for f in os.listdir(tmp_path) if f.endswith(".npy") or os.path.isdir(tmp_path / f)]
+    same = _run_bench(tmp_path, "--steps", "1", "--warmup", "0", "--full", "--dump-outputs", str(tmp_path / "a"))
+    assert 0.0 <= same["val_IIA"] <= 100.0 and 0.0 <= same["val_accuracy"] <= 100.0
+    assert same["last_train_losses"] == plain["last_train_losses"]  # the option does not touch the timed steps
+    longer = _run_bench(tmp_path, "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "b"))
+    assert longer["steps"] == 3 and longer["last_train_losses"] != plain["last_train_losses"]
+    dumps = []
+    for name in ("a", "b"):
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["train_behavior_loss.npy", "train_iit_loss.npy", "train_strict_loss.npy"]
+        arrays = {f: np.load(tmp_path / name / f) for f in files}
+        assert all(a.dtype == np.float64 and a.shape == (2,) and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+        dumps.append(arrays)
+    for f in dumps[0]:  # same seeded start state and batches, whatever ran before: exact on the CPU oracle backend
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+        assert dumps[0][f][0] != dumps[0][f][1]  # the second step saw the first step's updates
+    # the first replayed step is the run's first step (start state, first batch): --steps 1 --warmup 0 reported it
+    for k, v in plain["last_train_losses"].items():
+        assert float(dumps[0][k.replace("/", "_") + ".npy"][0]) == pytest.approx(v, abs=1e-4)
+
+
 def _decision_worker(rank, world, port, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
