@@ -82,6 +82,7 @@ hipError_t launch_tile(const G2Args& a, int tile, hipStream_t s) {
     // 192 workgroups for [768][3072] / [3072][768] / 144 for [768][2304] at half the operand bytes per flop of
     // 96 x 96 (the intake-bound regime); 3- and 2-deep rings
     // (tile 19 was 192 x 192 with a 3-deep ring: wrong results under the reduction split; not offered)
+    // (tile 20 serves mode 3 only: iit_gemm_glds_ok says why)
     case 20: return launch<192, 192, 2, AKM, BKM, EPI>(a, s);
     // 192 x 128 / 128 x 192 (2 x 2 waves of 96 x 64 / 64 x 96), 4-deep rings (exactly 160 KiB)
     case 21: return launch<192, 128, 4, AKM, BKM, EPI>(a, s);
@@ -145,6 +146,12 @@ IIT_EXPORT int iit_gemm_glds_ok(const void* A, const void* B, const void* C, con
     return 1;
   }
   if (tile < 0 || tile >= IIT_GLDS_TILES || tile == 19 || tile >= 35) return 0;
+  // tile 20 (192 x 192, 6 x 6 accumulators per wave) is offered for the weight gradients only: with a k-contiguous A
+  // (modes 0 / 2) its kernels need more than 256 VGPRs, and hipcc parks the destinations of the asm-issued
+  // ds_read_b128 fragment reads in AGPRs (v_accvgpr_write right after the issue, before the data has landed) and
+  // reuses the registers -- one 16-row fragment per wave row came out wrong (tests/test_gemm_exact.py).  The mode-3
+  // kernels hold no such copy and are exact.
+  if (tile == 20 && mode != 3) return 0;
   // atomic split-K: fp32 accumulate only; reduction split-K (``reduce``): fp32 accumulate, store or residual add (the
   // last-arriving split runs the epilogue once on the summed tile)
   const bool split_epi = epi == E_F32_ACC || (reduce && (epi == E_F32_STORE || epi == E_F32_RESID));

@@ -119,34 +119,36 @@ def _operands(A, B, M, N, Kd, lda, ldb, mode):
 
 
 def _mm_f32(a, b):
-    if _BLAS_OK.get("out_dtype", True):
+    # (the capability flags are per device type: a CPU call that lacks ``out_dtype`` must not send the GPU's fp32
+    # GEMMs to the fallback below, which rounds the product to bf16 -- tests/test_gemm_exact.py found exactly that)
+    if _BLAS_OK.get(("out_dtype", a.device.type), True):
         try:
             return torch.mm(a, b, out_dtype=F32)
         except (RuntimeError, TypeError):
-            _BLAS_OK["out_dtype"] = False
+            _BLAS_OK[("out_dtype", a.device.type)] = False
     return torch.mm(a, b).float()
 
 
 def _mm_f32_into(c, a, b) -> None:
     """c = a @ b (bf16 operands, fp32 output written straight into ``c``: beta = 0, no read of ``c``)."""
-    if _BLAS_OK.get("mm_out_dtype", True) and c.is_contiguous():
+    if _BLAS_OK.get(("mm_out_dtype", a.device.type), True) and c.is_contiguous():
         try:
             torch.mm(a, b, out_dtype=F32, out=c)
             return
         except (RuntimeError, TypeError):
-            _BLAS_OK["mm_out_dtype"] = False
+            _BLAS_OK[("mm_out_dtype", a.device.type)] = False
     c.copy_(_mm_f32(a, b))
 
 
 def _addmm_f32(c, base, a, b) -> None:
     """c = base + a @ b with bf16 operands, fp32 accumulate/output, in one hipBLASLt call when supported
     (``base`` may alias ``c``: the accumulate-into-gradient case)."""
-    if _BLAS_OK.get("addmm_dtype", True):
+    if _BLAS_OK.get(("addmm_dtype", a.device.type), True):
         try:
             torch.addmm(base, a, b, out_dtype=F32, out=c)
             return
         except (RuntimeError, TypeError):
-            _BLAS_OK["addmm_dtype"] = False
+            _BLAS_OK[("addmm_dtype", a.device.type)] = False
     if base is c:
         c.add_(_mm_f32(a, b))
     else:

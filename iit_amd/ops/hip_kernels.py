@@ -25,6 +25,10 @@ EPI_DGELU_ERF = 9  # EPI_DGELU with the exact (erf) GELU's derivative
 MODE_NN, MODE_AKM, MODE_BKM, MODE_AF32, MODE_BF32 = 0, 1, 2, 4, 8
 
 _LIB = None
+# group heights (M-tiles per column group) of the XCD-local tile order that ``lib()`` sets: single-problem LDS-DMA
+# launches / dual dX + dW launches (the measurements are quoted in ``lib()``)
+GEMM_GROUP_M = 4
+GEMM_DUAL_GROUP_M = 2
 
 _SIGS = {
     "iit_gemm": [c_void_p] * 10 + [c_long] * 5 + [c_int] * 12 + [c_void_p],
@@ -136,12 +140,12 @@ def lib():
         # XCD-local tile-order group height of the single-problem LDS-DMA launches: 4 M-tiles per column group
         # measured 0.2-0.3 % faster than 8 on the headline step over two alternating rounds on one box (16 slower;
         # profiles/launch_knobs_r4s2.txt); IIT_GEMM_GROUP_M overrides
-        gm = os.environ.get("IIT_GEMM_GROUP_M", "4")
+        gm = os.environ.get("IIT_GEMM_GROUP_M", str(GEMM_GROUP_M))
         if gm:
             L.iit_gemm_glds_set_group_m(int(gm))
         # the same for the dual dX + dW launches: 2 measured 0.2-0.4 % faster than the body's 8 over two alternating
         # rounds (4 in between, 16 slower; profiles/launch_knobs_r4s2.txt); IIT_GEMM_DUAL_GROUP_M overrides
-        dgm = os.environ.get("IIT_GEMM_DUAL_GROUP_M", "2")
+        dgm = os.environ.get("IIT_GEMM_DUAL_GROUP_M", str(GEMM_DUAL_GROUP_M))
         if dgm:
             L.iit_gemm_dual_set_group_m(int(dgm))
     return _LIB
@@ -230,7 +234,7 @@ GLDS_TILES = {0: (128, 128), 1: (128, 64), 2: (64, 128), 3: (64, 64), 4: (128, 1
               10: (96, 192), 11: (192, 96),  # 2-way reduction split: 256 workgroups for the [768][3072] gradients
               12: (96, 96), 13: (128, 96), 14: (64, 64),  # deep LDS rings (6 / 5 / 8 K-tiles)
               15: (128, 96), 16: (96, 96), 17: (64, 64), 18: (128, 128),  # 128-deep K-tiles (K % 128 == 0)
-              20: (192, 192),  # weight gradients with a 4-way reduction split (2-deep ring)
+              20: (192, 192),  # weight gradients (mode 3 only) with a 4-way reduction split (2-deep ring)
               21: (192, 128), 22: (128, 192),
               # two co-resident workgroups per CU (<= 80 KiB LDS each): prologue / epilogue overlap
               23: (128, 96), 24: (64, 96), 25: (128, 128), 26: (96, 96), 27: (128, 192), 28: (64, 192),
@@ -395,11 +399,14 @@ _PF_PER_MB = float(os.environ.get("IIT_DUAL_PREFETCH_WGS_PER_MB", "16"))
 
 
 def _prefetch_args(prefetch):
-    ts = [t for t in (prefetch or ()) if t is not None and t.is_cuda and t.is_contiguous()][:2]
+    # the prefetch workgroups issue one 4-byte load at the start of every 64-byte granule: whole granules only (a
+    # trailing part of 1-3 bytes would be read past the tensor's end), and a range with none is left out
+    ts = [t for t in (prefetch or ()) if t is not None and t.is_cuda and t.is_contiguous()
+          and t.numel() * t.element_size() >= 64][:2]
     if not ts or _PF_PER_MB <= 0:
         return (None, 0, None, 0, 0)
     ts += [None] * (2 - len(ts))
-    nb = [t.numel() * t.element_size() if t is not None else 0 for t in ts]
+    nb = [t.numel() * t.element_size() // 64 * 64 if t is not None else 0 for t in ts]
     wgs = max(8, min(1024, int(sum(nb) / 2 ** 20 * _PF_PER_MB)))
     return (_p(ts[0]), nb[0], _p(ts[1]), nb[1], wgs)
 
@@ -1054,3 +1061,8 @@ def gemm_glds_set_prof(buf) -> None:
 def gemm_glds_set_group_m(gm: int) -> None:
     """M-tiles per group of the LDS-DMA GEMM's XCD-local tile order for later launches (0 = default 8)."""
     lib().iit_gemm_glds_set_group_m(int(gm))
+
+
+def gemm_dual_set_group_m(gm: int) -> None:
+    """The same for both problems of the dual dX + dW launches (0 = default 8)."""
+    lib().iit_gemm_dual_set_group_m(int(gm))

@@ -38,7 +38,10 @@ int main() {
   for (int t = 0; t < ntiles; ++t) {
     const int M = bm[t] * 4, N = bn[t] * 2, K = 512;
     const int ok = iit_gemm_glds_ok(p, p, p, nullptr, nullptr, K, N, N, 0, 0, M, N, K, 2, 0, 0, t, 1, 0);
-    CHECK(ok == (t == 19 ? 0 : 1));  // tile 19 is withdrawn
+    // tile 19 is withdrawn; tile 20 serves the weight gradients (mode 3) only
+    CHECK(ok == (t == 19 || t == 20 ? 0 : 1));
+    const int ok3 = iit_gemm_glds_ok(p, p, p, nullptr, nullptr, M, N, N, 0, 0, M, N, K, 3, 7, 0, t, 1, 0);
+    CHECK(ok3 == (t == 19 ? 0 : 1));
     CHECK(!iit_gemm_glds_ok(p, p, p, nullptr, nullptr, K, N, N, 0, 0, M + 1, N, K, 2, 0, 0, t, 1, 0));
     CHECK(!iit_gemm_glds_ok(p, p, p, nullptr, nullptr, K + 1, N, N, 0, 0, M, N, K, 2, 0, 0, t, 1, 0));
     CHECK(!iit_gemm_glds_ok((const char*)p + 2, p, p, nullptr, nullptr, K, N, N, 0, 0, M, N, K, 2, 0, 0, t, 1, 0));
