@@ -521,14 +521,44 @@ bool args_ok(const FaArgs& a, int dh) {
   return (al & 15) == 0;
 }
 
+// 16-row blocks per wave of a launch over ``heads`` heads: 2 halves the LDS traffic per FLOP but halves the workgroup
+// count -- taken when that still leaves >= 2 workgroups per CU.  ``blocks`` 1 | 2 forces the count (per call: the
+// exact tests run both variants in one process), 0 leaves it to IIT_FLASH_QB=1|2 and then to the grid size.
+int fa_blocks(int blocks, int S, int heads, int B) {
+  static const int qb_env = getenv("IIT_FLASH_QB") ? atoi(getenv("IIT_FLASH_QB")) : 0;
+  const int want = blocks ? blocks : qb_env;
+  if (want == 1 || want == 2) return want;
+  return (long)((S + 2 * T64 - 1) / (2 * T64)) * heads * B >= 512 ? 2 : 1;
+}
+
+// the dK/dV kernel keeps one block per wave at dh 128 (its accumulators would not fit two waves per SIMD)
+int fa_blocks_dkdv(int blocks, int S, int Hkv, int B, int dh) { return dh == 128 ? 1 : fa_blocks(blocks, S, Hkv, B); }
+
+int fa_grid_x(int S, int nb) { return (S + T64 * nb - 1) / (T64 * nb); }
+
 }  // namespace
+
+// The launch plan of iit_flash_fwd_blocks / iit_flash_bwd_blocks for ``blocks`` (pure host arithmetic, no device
+// call): out4 = {blocks per wave of the forward and dQ kernels, of the dK/dV kernel, grid.x of the forward / dQ
+// launch, grid.x of the dK/dV launch}.
+IIT_EXPORT int iit_flash_plan(int B, int S, int Hq, int Hkv, int dh, int blocks, int* out4) {
+  if (blocks < 0 || blocks > 2 || B <= 0 || S <= 0 || Hq <= 0 || Hkv <= 0 || !(dh == 64 || dh == 128))
+    return (int)hipErrorInvalidValue;
+  out4[0] = fa_blocks(blocks, S, Hq, B);
+  out4[1] = fa_blocks_dkdv(blocks, S, Hkv, B, dh);
+  out4[2] = fa_grid_x(S, out4[0]);
+  out4[3] = fa_grid_x(S, out4[1]);
+  return 0;
+}
 
 // q [B,S,Hq,dh], k/v [B,S,Hkv,dh] (bf16, any batch/position/head strides that keep 16-B rows), z [B,S,Hq,dh] bf16,
 // lse [B,Hq,S] fp32.  ``scale`` multiplies the scores (1/sqrt(dh) for standard attention).
-IIT_EXPORT int iit_flash_fwd(const void* q, const void* k, const void* v, const long* strides9, void* z,
-                             const long* zstrides3, float* lse, const void* src, const long* sstrides3,
-                             unsigned long long head_mask, int B, int S, int Hq, int Hkv, int dh, float scale,
-                             int causal, const void* spec, void* stream) {
+// ``blocks``: 16-query blocks per wave, 0 = the policy of fa_blocks, 1 | 2 forced.
+IIT_EXPORT int iit_flash_fwd_blocks(const void* q, const void* k, const void* v, const long* strides9, void* z,
+                                    const long* zstrides3, float* lse, const void* src, const long* sstrides3,
+                                    unsigned long long head_mask, int B, int S, int Hq, int Hkv, int dh, float scale,
+                                    int causal, const void* spec, void* stream, int blocks) {
+  if (blocks < 0 || blocks > 2) return (int)hipErrorInvalidValue;
   FaArgs a = {};
   a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v;
   a.qb = strides9[0]; a.qs = strides9[1]; a.qh = strides9[2];
@@ -545,12 +575,8 @@ IIT_EXPORT int iit_flash_fwd(const void* q, const void* k, const void* v, const 
     return (int)hipErrorInvalidValue;
   a.B = B; a.S = S; a.Hq = Hq; a.Hkv = Hkv; a.causal = causal; a.scale = scale;
   if (!args_ok(a, dh) || a.zs % 8 || a.zh % 8 || ((uintptr_t)z & 15)) return (int)hipErrorInvalidValue;
-  // query blocks per wave: 2 halves the LDS traffic per FLOP but halves the workgroup count -- taken when that
-  // still leaves >= 2 workgroups per CU (IIT_FLASH_QB=1|2 forces a choice)
-  static const int qb_env = getenv("IIT_FLASH_QB") ? atoi(getenv("IIT_FLASH_QB")) : 0;
-  const long wg2 = (long)((S + 2 * T64 - 1) / (2 * T64)) * Hq * B;
-  const int QB = qb_env == 1 ? 1 : (qb_env == 2 ? 2 : (wg2 >= 512 ? 2 : 1));
-  dim3 grid((S + T64 * QB - 1) / (T64 * QB), Hq, B);
+  const int QB = fa_blocks(blocks, S, Hq, B);
+  dim3 grid(fa_grid_x(S, QB), Hq, B);
   hipStream_t s = (hipStream_t)stream;
   if (dh == 64) {
     if (QB == 2) hipLaunchKernelGGL((fa_fwd_kernel<64, 2>), grid, dim3(256), 0, s, a);
@@ -562,12 +588,22 @@ IIT_EXPORT int iit_flash_fwd(const void* q, const void* k, const void* v, const 
   return (int)hipGetLastError();
 }
 
-// dz/z [B,S,Hq,dh] (z = the forward output), dd [B,Hq,S] fp32 scratch; dq/dk/dv with their own strides.
-IIT_EXPORT int iit_flash_bwd(const void* q, const void* k, const void* v, const long* strides9, const void* z,
-                             const long* zstrides3, const void* dz, const long* dzstrides3, const float* lse,
-                             float* dd, void* dq, void* dk, void* dv, const long* gstrides9,
+IIT_EXPORT int iit_flash_fwd(const void* q, const void* k, const void* v, const long* strides9, void* z,
+                             const long* zstrides3, float* lse, const void* src, const long* sstrides3,
                              unsigned long long head_mask, int B, int S, int Hq, int Hkv, int dh, float scale,
                              int causal, const void* spec, void* stream) {
+  return iit_flash_fwd_blocks(q, k, v, strides9, z, zstrides3, lse, src, sstrides3, head_mask, B, S, Hq, Hkv, dh, scale,
+                              causal, spec, stream, 0);
+}
+
+// dz/z [B,S,Hq,dh] (z = the forward output), dd [B,Hq,S] fp32 scratch; dq/dk/dv with their own strides.
+// ``blocks`` as in the forward, for the dQ and the dK/dV kernel (which keeps 1 at dh 128 whatever is asked).
+IIT_EXPORT int iit_flash_bwd_blocks(const void* q, const void* k, const void* v, const long* strides9, const void* z,
+                                    const long* zstrides3, const void* dz, const long* dzstrides3, const float* lse,
+                                    float* dd, void* dq, void* dk, void* dv, const long* gstrides9,
+                                    unsigned long long head_mask, int B, int S, int Hq, int Hkv, int dh, float scale,
+                                    int causal, const void* spec, void* stream, int blocks) {
+  if (blocks < 0 || blocks > 2) return (int)hipErrorInvalidValue;
   FaArgs a = {};
   a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v;
   a.qb = strides9[0]; a.qs = strides9[1]; a.qh = strides9[2];
@@ -595,13 +631,8 @@ IIT_EXPORT int iit_flash_bwd(const void* q, const void* k, const void* v, const 
   hipStream_t s = (hipStream_t)stream;
   const long rows = (long)B * Hq * S;
   dim3 gp((rows + 255) / 256);
-  // blocks per wave as in the forward: 2 when the grid keeps >= 2 workgroups per CU (IIT_FLASH_QB forces);
-  // the dK/dV kernel keeps one block per wave at dh 128 (its accumulators would not fit two waves per SIMD)
-  static const int qb_env = getenv("IIT_FLASH_QB") ? atoi(getenv("IIT_FLASH_QB")) : 0;
-  const int tiles2 = (S + 2 * T64 - 1) / (2 * T64);
-  const int nbq = qb_env == 1 ? 1 : (qb_env == 2 ? 2 : ((long)tiles2 * Hq * B >= 512 ? 2 : 1));
-  const int nbk = dh == 128 ? 1 : (qb_env == 1 ? 1 : (qb_env == 2 ? 2 : ((long)tiles2 * Hkv * B >= 512 ? 2 : 1)));
-  dim3 gkv((S + T64 * nbk - 1) / (T64 * nbk), Hkv, B), gq((S + T64 * nbq - 1) / (T64 * nbq), Hq, B);
+  const int nbq = fa_blocks(blocks, S, Hq, B), nbk = fa_blocks_dkdv(blocks, S, Hkv, B, dh);
+  dim3 gkv(fa_grid_x(S, nbk), Hkv, B), gq(fa_grid_x(S, nbq), Hq, B);
   if (dh == 64) {
     hipLaunchKernelGGL(fa_bwd_prep_kernel<64>, gp, dim3(256), 0, s, a);
     if (nbk == 2) hipLaunchKernelGGL((fa_bwd_dkdv_kernel<64, 2>), gkv, dim3(256), 0, s, a);
@@ -615,4 +646,13 @@ IIT_EXPORT int iit_flash_bwd(const void* q, const void* k, const void* v, const 
     else hipLaunchKernelGGL((fa_bwd_dq_kernel<128, 1>), gq, dim3(256), 0, s, a);
   }
   return (int)hipGetLastError();
+}
+
+IIT_EXPORT int iit_flash_bwd(const void* q, const void* k, const void* v, const long* strides9, const void* z,
+                             const long* zstrides3, const void* dz, const long* dzstrides3, const float* lse,
+                             float* dd, void* dq, void* dk, void* dv, const long* gstrides9,
+                             unsigned long long head_mask, int B, int S, int Hq, int Hkv, int dh, float scale,
+                             int causal, const void* spec, void* stream) {
+  return iit_flash_bwd_blocks(q, k, v, strides9, z, zstrides3, dz, dzstrides3, lse, dd, dq, dk, dv, gstrides9, head_mask,
+                              B, S, Hq, Hkv, dh, scale, causal, spec, stream, 0);
 }

@@ -812,6 +812,9 @@ IIT_EXPORT int iit_ln_bwd_sel(const void* dy, int dy_f32, const float* x, const 
 }
 
 // ============================================================================ attention (S <= 64)
+// The kernels keep q, k, v (the backward dz too) and the [S][S+1] score tables in dynamic LDS as fp32: a request
+// above the CU's 160 KiB cannot be met and is refused before the launch (the backward's at S = 64, dh = 128).
+constexpr size_t kAttnSmallLdsMax = 160 * 1024;
 // qkv: [B*S, ld_qkv] bf16 with q at column h*dh, k at HD + h*dh, v at 2*HD + h*dh (HD = H*dh).
 // z:   [B*S, ld_z] bf16 at column h*dh.  lse: [B*H*S] fp32.
 // head_mask bit h set => z[:, h] := zsrc[:, h] (interchange splice of hook_z).
@@ -886,6 +889,7 @@ IIT_EXPORT int iit_attn_small_fwd(const void* qkv, void* z, float* lse, const vo
                                   int causal, void* stream) {
   if (S > 64 || dh > 128) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(3 * S * (dh + 1) + S * (S + 1)) * sizeof(float);
+  if (lds > kAttnSmallLdsMax) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(attn_small_fwd_kernel, dim3(B * H), dim3(64), lds, (hipStream_t)stream, (const __bf16*)qkv,
                      (__bf16*)z, lse, (const __bf16*)zsrc, head_mask, B, S, H, dh, ld_qkv, ld_z, ld_src, scale, causal);
   return hipGetLastError();
@@ -967,6 +971,7 @@ IIT_EXPORT int iit_attn_small_bwd(const void* qkv, const void* dz, const float* 
                                   float scale, int causal, void* stream) {
   if (S > 64 || dh > 128) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(4 * S * (dh + 1) + 2 * S * (S + 1)) * sizeof(float);
+  if (lds > kAttnSmallLdsMax) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(attn_small_bwd_kernel, dim3(B * H), dim3(64), lds, (hipStream_t)stream, (const __bf16*)qkv,
                      (const __bf16*)dz, lse, (__bf16*)dqkv, head_mask, B, S, H, dh, ld_qkv, ld_dz, scale, causal);
   return hipGetLastError();

@@ -92,6 +92,11 @@ _SIGS = {
     "iit_flash_fwd": [c_void_p] * 3 + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ull] + [c_int] * 5
                      + [c_float, c_int, c_void_p, c_void_p],
     "iit_flash_bwd": [c_void_p] * 3 + [c_void_p] * 11 + [c_ull] + [c_int] * 5 + [c_float, c_int, c_void_p, c_void_p],
+    "iit_flash_fwd_blocks": [c_void_p] * 3 + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ull]
+                            + [c_int] * 5 + [c_float, c_int, c_void_p, c_void_p, c_int],
+    "iit_flash_bwd_blocks": [c_void_p] * 3 + [c_void_p] * 11 + [c_ull] + [c_int] * 5 + [c_float, c_int, c_void_p,
+                                                                                       c_void_p, c_int],
+    "iit_flash_plan": [c_int] * 6 + [c_void_p],
     "iit_splice": [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_float, c_void_p],
     "iit_splice_spec_size": [],
     "iit_bn_fwd": [c_void_p] * 8 + [c_long, c_int, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p,
@@ -560,6 +565,23 @@ def _mfma_attn(S, dh):
     return S <= 16 and dh in (32, 64, 96, 128) and os.environ.get("IIT_ATTN", "mfma") == "mfma"
 
 
+ATTN_SMALL_LDS_MAX = 160 * 1024  # dynamic LDS a workgroup of the VALU S <= 64 kernels can get (one CU's)
+
+
+def attn_small_lds(S: int, dh: int, backward: bool) -> int:
+    """Bytes of dynamic LDS ``iit_attn_small_fwd`` / ``iit_attn_small_bwd`` (csrc/kernels.hip) ask for: q, k, v (and
+    dz) rows padded by one float plus one / two [S][S+1] score tables, all fp32."""
+    return ((4 * S * (dh + 1) + 2 * S * (S + 1)) if backward else (3 * S * (dh + 1) + S * (S + 1))) * 4
+
+
+def attn_small_ok(S: int, dh: int) -> bool:
+    """Whether the short-sequence kernels serve (S, dh) forward and backward: the MFMA kernel, or a VALU launch whose
+    backward fits the LDS (the exports refuse a larger request)."""
+    if S > 64 or dh > 128:
+        return False
+    return _mfma_attn(S, dh) or attn_small_lds(S, dh, True) <= ATTN_SMALL_LDS_MAX
+
+
 def attn_small_fwd(qkv, z, lse, zsrc, head_mask, B, S, H, dh, ld_qkv, ld_z, ld_src, scale, causal):
     """Causal attention for S <= 64 (MFMA one-wave-per-head kernel when S <= 16, csrc/attn_mfma.hip)."""
     if CHECK_BOUNDS:
@@ -635,32 +657,52 @@ def _longs(vals):
     return (c_long * len(vals))(*vals)
 
 
-def flash_fwd(q, k, v, z, lse, src, head_mask: int, scale: float, causal: bool, spec=None):
+def _flash_blocks(blocks: int) -> int:
+    if blocks not in (0, 1, 2):
+        raise ValueError(f"flash attention: blocks must be 0 (the launch policy), 1 or 2, got {blocks!r}")
+    return int(blocks)
+
+
+def flash_plan(B: int, S: int, Hq: int, Hkv: int, dh: int, blocks: int = 0) -> dict:
+    """The launch plan of :func:`flash_fwd` / :func:`flash_bwd` for ``blocks`` (host arithmetic only): 16-row blocks
+    per wave of the forward / dQ kernels (``nb_q``) and of the dK/dV kernel (``nb_kv``, always 1 at dh 128), and the
+    launches' ``grid.x``."""
+    out = (c_int * 4)()
+    _check(lib().iit_flash_plan(B, S, Hq, Hkv, dh, _flash_blocks(blocks), ctypes.cast(out, c_void_p)), "flash_plan")
+    return {"nb_q": out[0], "nb_kv": out[1], "grid_q": out[2], "grid_kv": out[3]}
+
+
+def flash_fwd(q, k, v, z, lse, src, head_mask: int, scale: float, causal: bool, spec=None, blocks: int = 0):
     """Tiled attention forward (csrc/flash_attn.hip): q/z [B,S,Hq,dh], k/v [B,S,Hkv,dh], lse [B,Hq,S] fp32.
     ``spec`` (a :class:`iit_amd.ops.splice.PatchSpec` over z's [B,S,Hq,dh] with ``src``'s strides): general splice of
-    the output, applied by the output store (replaces ``head_mask``)."""
+    the output, applied by the output store (replaces ``head_mask``).  ``blocks``: 16-query blocks per wave, 0 = the
+    library's policy, 1 / 2 forced."""
+    blocks = _flash_blocks(blocks)
     B, S, Hq, dh = q.shape
     Hkv = k.shape[2]
     st = _longs(_bsh(q) + _bsh(k) + _bsh(v))
     zs = _longs(_bsh(z))
     ss = _longs(_bsh(src)) if (src is not None and spec is None) else None
-    _check(lib().iit_flash_fwd(_p(q), _p(k), _p(v), ctypes.cast(st, c_void_p), _p(z), ctypes.cast(zs, c_void_p),
-                               _p(lse), _p(src), None if ss is None else ctypes.cast(ss, c_void_p),
-                               head_mask if src is not None else 0, B, S, Hq, Hkv, dh, scale, int(causal),
-                               None if spec is None else spec.ptr, _stream()),
+    _check(lib().iit_flash_fwd_blocks(_p(q), _p(k), _p(v), ctypes.cast(st, c_void_p), _p(z), ctypes.cast(zs, c_void_p),
+                                      _p(lse), _p(src), None if ss is None else ctypes.cast(ss, c_void_p),
+                                      head_mask if src is not None else 0, B, S, Hq, Hkv, dh, scale, int(causal),
+                                      None if spec is None else spec.ptr, _stream(), blocks),
            "flash_fwd")
 
 
-def flash_bwd(q, k, v, z, dz, lse, dd, dq, dk, dv, head_mask: int, scale: float, causal: bool, spec=None):
+def flash_bwd(q, k, v, z, dz, lse, dd, dq, dk, dv, head_mask: int, scale: float, causal: bool, spec=None,
+              blocks: int = 0):
+    """``blocks`` as in :func:`flash_fwd`, for the dQ and dK/dV kernels (dK/dV keeps 1 at dh 128)."""
+    blocks = _flash_blocks(blocks)
     B, S, Hq, dh = q.shape
     Hkv = k.shape[2]
     st = _longs(_bsh(q) + _bsh(k) + _bsh(v))
     gs = _longs(_bsh(dq) + _bsh(dk) + _bsh(dv))
     zs, ds = _longs(_bsh(z)), _longs(_bsh(dz))
-    _check(lib().iit_flash_bwd(_p(q), _p(k), _p(v), ctypes.cast(st, c_void_p), _p(z), ctypes.cast(zs, c_void_p),
-                               _p(dz), ctypes.cast(ds, c_void_p), _p(lse), _p(dd), _p(dq), _p(dk), _p(dv),
-                               ctypes.cast(gs, c_void_p), head_mask, B, S, Hq, Hkv, dh, scale, int(causal),
-                               None if spec is None else spec.ptr, _stream()),
+    _check(lib().iit_flash_bwd_blocks(_p(q), _p(k), _p(v), ctypes.cast(st, c_void_p), _p(z), ctypes.cast(zs, c_void_p),
+                                      _p(dz), ctypes.cast(ds, c_void_p), _p(lse), _p(dd), _p(dq), _p(dk), _p(dv),
+                                      ctypes.cast(gs, c_void_p), head_mask, B, S, Hq, Hkv, dh, scale, int(causal),
+                                      None if spec is None else spec.ptr, _stream(), blocks),
            "flash_bwd")
 
 

@@ -1768,7 +1768,7 @@ class HipOps(TorchOps):
                 z = z.clone()
                 z[:, :, list(patch_heads)] = patch_src[:, :, list(patch_heads)].to(z.dtype)
             return z
-        if S > 64 or dh > 128:
+        if not K.attn_small_ok(S, dh):  # S > 64, dh > 128, or a backward that would not fit the LDS
             z = TorchOps.attention(self, q, k, v, causal, attn_scale)
             if patch_heads:
                 z = z.clone()

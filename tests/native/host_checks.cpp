@@ -15,6 +15,7 @@ int iit_gemm_glds_ok(const void* A, const void* B, const void* C, const void* C2
 int iit_adam_span_size();
 int iit_splice_spec_size();
 int iit_shadow_desc_size();
+int iit_flash_plan(int B, int S, int Hq, int Hkv, int dh, int blocks, int* out4);
 }
 
 static int failures = 0;
@@ -54,6 +55,19 @@ int main() {
   CHECK(iit_adam_span_size() == 24);
   CHECK(iit_splice_spec_size() == 320);
   CHECK(iit_shadow_desc_size() > 0);
+  // flash attention launch plan {blocks per wave fwd / dQ, dK/dV, grid.x fwd / dQ, dK/dV}: a forced block count
+  // reaches every launch that has the variant (dK/dV at dh 128 keeps one block), 0 is the grid-size policy
+  {
+    int p[4];
+    CHECK(iit_flash_plan(2, 129, 4, 2, 64, 1, p) == 0 && p[0] == 1 && p[1] == 1 && p[2] == 3 && p[3] == 3);
+    CHECK(iit_flash_plan(2, 129, 4, 2, 64, 2, p) == 0 && p[0] == 2 && p[1] == 2 && p[2] == 2 && p[3] == 2);
+    CHECK(iit_flash_plan(2, 129, 4, 2, 128, 2, p) == 0 && p[0] == 2 && p[1] == 1 && p[2] == 2 && p[3] == 3);
+    CHECK(iit_flash_plan(2, 129, 4, 2, 64, 0, p) == 0 && p[0] == 1 && p[1] == 1);
+    CHECK(iit_flash_plan(16, 130, 16, 16, 64, 0, p) == 0 && p[0] == 2 && p[1] == 2 && p[2] == 2);
+    CHECK(iit_flash_plan(16, 130, 16, 4, 64, 0, p) == 0 && p[0] == 2 && p[1] == 1 && p[3] == 3);
+    CHECK(iit_flash_plan(2, 129, 4, 2, 64, 3, p) != 0 && iit_flash_plan(2, 129, 4, 2, 64, -1, p) != 0);
+    CHECK(iit_flash_plan(2, 129, 4, 2, 96, 1, p) != 0);
+  }
   // heap round trip under ASan: a packed range table copied the way the splice launcher reads it
   std::vector<uint8_t> spec(iit_splice_spec_size(), 0);
   uint8_t copy[512];

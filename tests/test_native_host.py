@@ -16,7 +16,7 @@ def test_host_checks_under_asan(tmp_path):
     # gemm_glds.hip dispatches its 256 x 256 tiles to gemm_8ph.hip / gemm_4w.hip: link them too
     src = [os.path.join(ROOT, "tests", "native", "host_checks.cpp")] + [
         os.path.join(ROOT, "csrc", f) for f in ("gemm_glds.hip", "gemm_8ph.hip", "gemm_4w.hip", "kernels.hip",
-                                                "splice.hip")]
+                                                "splice.hip", "flash_attn.hip")]
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "csrc"),
            "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fno-omit-frame-pointer", "-o", exe] + src
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
