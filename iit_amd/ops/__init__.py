@@ -3,6 +3,9 @@
 * ``torch`` – :class:`TorchOps`, reference semantics, any device / dtype (oracle).
 * ``hip``   – :class:`iit_amd.ops.hip_ops.HipOps`, hand-written gfx950 kernels
   (bf16 activations, fp32 accumulation / residual stream / master weights).
+* ``hip32`` – :class:`iit_amd.ops.hip32_ops.HipF32Ops`, ``TorchOps`` in fp32 with the
+  projections on the exact-fp32 MFMA GEMM (``csrc/gemm_f32.hip``).  Opt-in only:
+  ``backend=None`` never selects it; on a CPU model or without the extension it raises.
 
 ``select_ops(model, backend)`` picks per call: ``backend=None`` means "hip when
 the model lives on a GPU and computes in bf16, else torch".  Asking for ``hip``
@@ -50,6 +53,11 @@ def select_ops(model, backend: Optional[str] = None):
             raise RuntimeError("hip op backend requires the model on a GPU")
         from .hip_ops import get_hip_ops
         return get_hip_ops(model)
+    if backend == "hip32":  # opt-in only: ``backend=None`` never selects it
+        if not on_gpu:
+            raise RuntimeError("hip32 op backend requires the model on a GPU")
+        from .hip32_ops import get_hip32_ops
+        return get_hip32_ops(model)
     raise ValueError(f"unknown op backend {backend}")
 
 

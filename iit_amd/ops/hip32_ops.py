@@ -1,0 +1,265 @@
+"""``hip32``: an opt-in op backend that runs an fp32 model's projections on the exact-fp32 MFMA GEMM
+(``csrc/gemm_f32.hip``, :func:`iit_amd.ops.hip_kernels.gemm_f32`).
+
+:class:`HipF32Ops` is :class:`~iit_amd.ops.torch_ops.TorchOps` in fp32 with ``lin`` (and through it ``mlp_in``,
+``mlp_out``, ``unembed``), ``qkv`` and ``o_proj`` replaced; attention, LayerNorm, GELU, the loss and the optimizer
+stay where the fp32 torch path has them.  Gradients are returned to autograd exactly as ``x @ W`` returns them
+(no direct arena accumulation).  The backend is never chosen automatically: ``select_ops(model, "hip32")`` or
+``model.set_op_backend("hip32")``.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import hip_kernels as K
+from .torch_ops import TorchOps, act_fn
+
+
+def _up4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+def _operand(t: torch.Tensor) -> torch.Tensor:
+    """``t [rows][cols]`` as the kernel takes it -- unit column stride, a row pitch that is a multiple of 4 elements,
+    a 16-byte aligned base -- copying into a padded buffer only when ``t`` is not already so."""
+    rows, cols = t.shape
+    if (t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= cols
+            and t.data_ptr() % 16 == 0):
+        return t
+    buf = torch.empty(rows, _up4(cols), dtype=torch.float32, device=t.device)[:, :cols]
+    buf.copy_(t)
+    return buf
+
+
+def _out(rows: int, cols: int, device) -> torch.Tensor:
+    """Uninitialised fp32 ``[rows][cols]`` output whose row pitch is a multiple of 4 elements."""
+    return torch.empty(rows, _up4(cols), dtype=torch.float32, device=device)[:, :cols]
+
+
+def _tile(M: int, N: int) -> int:
+    """The 128 x 128 tile once its tiles alone give every CU a workgroup and neither extent leaves half of it
+    empty, else 64 x 64 (a stated policy)."""
+    return 1 if min(M, N) >= 128 and ((M + 127) // 128) * ((N + 127) // 128) >= K.N_CU else 0
+
+
+def _gemm(A, B, C, M, N, Kd, mode, epi=K.EPI_F32_STORE, bias=None, resid=None):
+    tile = _tile(M, N)
+    K.gemm_f32(A, B, C, M=M, N=N, K=Kd, lda=A.stride(0), ldb=B.stride(0), ldc=C.stride(0), mode=mode, epi=epi,
+               bias=bias, resid=resid, ldr=0 if resid is None else resid.stride(0), tile=tile,
+               splits=K.gemm_f32_splits(M, N, Kd, tile))
+
+
+def _forward(x2, W2, b, r2=None):
+    """``x2 [T][K] @ W2 [K][N] (+ b) (+ r2)``: one mode-2 GEMM, bias and residual in its epilogue."""
+    T, Kd = x2.shape
+    N = W2.shape[1]
+    y = _out(T, N, x2.device)
+    _gemm(x2, W2, y, T, N, Kd, K.MODE_BKM, K.EPI_F32_STORE if r2 is None else K.EPI_F32_RESID, b, r2)
+    return y
+
+
+def _backward(x2, W2, dy2, need_x: bool, need_w: bool):
+    """``(dX = dY W^T`` by a mode-0 GEMM, ``dW = X^T dY`` by a mode-3 GEMM); W2 ``[K][N]`` serves both as stored."""
+    T, Kd = x2.shape
+    N = W2.shape[1]
+    dx = dw = None
+    if need_x:
+        dx = _out(T, Kd, x2.device)
+        _gemm(dy2, W2, dx, T, Kd, N, K.MODE_NN)
+    if need_w:
+        dw = _out(Kd, N, x2.device)
+        _gemm(x2, dy2, dw, Kd, N, T, K.MODE_AKM | K.MODE_BKM)
+    return dx, dw
+
+
+def weight_ok(x2: torch.Tensor, W2: torch.Tensor) -> bool:
+    """Whether ``x2 @ W2`` can take the kernel: fp32 on the GPU, a 2-D weight with unit column stride that passes
+    ``gemm_f32_ok`` (aligned base, row pitch a multiple of 4).  ``x2`` is an operand as :func:`_operand` returns it
+    and also stands in for the output, which the function allocates aligned."""
+    if not (x2.is_cuda and W2.is_cuda and x2.dtype == torch.float32 and W2.dtype == torch.float32 and W2.dim() == 2
+            and W2.stride(1) == 1 and x2.shape[0] > 0):
+        return False
+    return K.gemm_f32_ok(x2, W2, x2, M=x2.shape[0], N=W2.shape[1], K=x2.shape[1], lda=x2.stride(0),
+                         ldb=W2.stride(0), ldc=_up4(W2.shape[1]), mode=K.MODE_BKM, epi=K.EPI_F32_STORE)
+
+
+class LinearF32Fn(torch.autograd.Function):
+    """``y = x @ W2 (+ b) (+ resid)`` for fp32 ``x [..., K]`` and a weight ``W2 [K][N]`` with unit column stride (any
+    aligned row pitch: the arena's padded ``W_U`` is taken as stored).  The backward returns ``dX``, ``dW``,
+    ``db = colsum(dY)`` (``sum(0)``: a fixed-order reduction) and ``dresid = dY`` to autograd."""
+
+    @staticmethod
+    def forward(ctx, x, W2, b, resid=None):
+        Kd, N = W2.shape
+        lead = x.shape[:-1]
+        x2 = _operand(x.reshape(-1, Kd))
+        r2 = None if resid is None else _operand(resid.reshape(-1, N))
+        ctx.save_for_backward(x2, W2)
+        ctx.lead, ctx.has_b, ctx.has_r = lead, b is not None, resid is not None
+        return _forward(x2, W2, b, r2).view(*lead, N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, W2 = ctx.saved_tensors
+        Kd, N = W2.shape
+        dy2 = _operand(dy.reshape(-1, N))
+        dx, dw = _backward(x2, W2, dy2, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        db = dy2.sum(0) if ctx.has_b and ctx.needs_input_grad[2] else None
+        dr = dy if ctx.has_r and ctx.needs_input_grad[3] else None
+        return None if dx is None else dx.view(*ctx.lead, Kd), dw, db, dr
+
+
+class QKVF32Fn(torch.autograd.Function):
+    """The packed QKV projection: ``W_Q | W_K | W_V`` in the arena layout of ``qkv_arena_groups`` are one
+    ``[d][(H + 2 H_kv) dh]`` matrix, so the three projections are one GEMM, and so are their input gradient and
+    their weight gradient; the three weight (bias) gradients are strided views of one ``[d][N]`` (``[N]``) buffer."""
+
+    @staticmethod
+    def forward(ctx, x, W_Q, W_K, W_V, b_Q, b_K, b_V):
+        H, d, dh = W_Q.shape
+        Hkv = W_K.shape[0]
+        N = (H + 2 * Hkv) * dh
+        Wp = W_Q.detach().as_strided((d, N), (N, 1))
+        bp = b_Q.detach().as_strided((N,), (1,))
+        lead = x.shape[:-1]
+        x2 = _operand(x.reshape(-1, d))
+        ctx.save_for_backward(x2, Wp)
+        ctx.lead, ctx.dims = lead, (H, Hkv, dh)
+        y = _forward(x2, Wp, bp).view(*lead, N)
+        return (y[..., :H * dh].view(*lead, H, dh), y[..., H * dh:(H + Hkv) * dh].view(*lead, Hkv, dh),
+                y[..., (H + Hkv) * dh:].view(*lead, Hkv, dh))
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        x2, Wp = ctx.saved_tensors
+        H, Hkv, dh = ctx.dims
+        d, N = Wp.shape
+        T = x2.shape[0]
+        dy2 = _out(T, N, x2.device)
+        c0 = 0
+        for g, n in zip((dq, dk, dv), (H * dh, Hkv * dh, Hkv * dh)):
+            if g is None:
+                dy2[:, c0:c0 + n].zero_()
+            else:
+                dy2[:, c0:c0 + n].copy_(g.reshape(T, n))
+            c0 += n
+        need = ctx.needs_input_grad
+        dx, dw = _backward(x2, Wp, dy2, need[0], any(need[1:4]))
+        gw = [None] * 3
+        gb = [None] * 3
+        spans = ((0, H), (H, Hkv), (H + Hkv, Hkv))
+        if dw is not None:
+            dw3 = dw.view(d, H + 2 * Hkv, dh)
+            gw = [dw3[:, c:c + n].permute(1, 0, 2) if need[1 + i] else None for i, (c, n) in enumerate(spans)]
+        if any(need[4:7]):
+            db = dy2.sum(0).view(H + 2 * Hkv, dh)
+            gb = [db[c:c + n] if need[4 + i] else None for i, (c, n) in enumerate(spans)]
+        return (None if dx is None else dx.view(*ctx.lead, d), *gw, *gb)
+
+
+def _same_storage(*ts) -> bool:
+    p = ts[0].untyped_storage().data_ptr()
+    return all(t.untyped_storage().data_ptr() == p for t in ts)
+
+
+def packed_qkv(W_Q, W_K, W_V, b_Q, b_K, b_V) -> bool:
+    """Whether the six parameters have the packed arena layout of ``qkv_arena_groups``: weights ``[H][d][dh]`` with
+    strides ``(dh, N, 1)`` at adjacent offsets of one buffer, biases packed contiguously in the same order."""
+    if W_Q.dim() != 3 or any(b is None for b in (b_Q, b_K, b_V)):
+        return False
+    H, d, dh = W_Q.shape
+    Hkv = W_K.shape[0]
+    N = (H + 2 * Hkv) * dh
+    ws, bs = (W_Q, W_K, W_V), (b_Q, b_K, b_V)
+    if W_K.shape != (Hkv, d, dh) or W_V.shape != (Hkv, d, dh) or any(w.stride() != (dh, N, 1) for w in ws):
+        return False
+    if b_Q.shape != (H, dh) or b_K.shape != (Hkv, dh) or b_V.shape != (Hkv, dh) or not all(
+            b.is_contiguous() for b in bs):
+        return False
+    if not (_same_storage(*ws) and _same_storage(*bs)):
+        return False
+    offs = (0, H * dh * 4, (H + Hkv) * dh * 4)
+    return all(w.data_ptr() == W_Q.data_ptr() + o and b.data_ptr() == b_Q.data_ptr() + o
+               for w, b, o in zip(ws, bs, offs))
+
+
+class HipF32Ops(TorchOps):
+    """fp32 :class:`TorchOps` whose projections run on ``csrc/gemm_f32.hip``.  ``calls`` counts, per op, the calls
+    that took the kernel (``"qkv"``, ``"o_proj"``, ``"mlp_in"``, ``"mlp_out"``, ``"unembed"``, ``"lin"``) and those
+    that fell back to the inherited torch op (``"<op>_fallback"``)."""
+    name = "hip32"
+    fused = False
+    calls: dict = {}
+
+    def __init__(self):
+        super().__init__(torch.float32)
+
+    @classmethod
+    def _count(cls, op: str) -> None:
+        cls.calls[op] = cls.calls.get(op, 0) + 1
+
+    def _lin(self, op: str, x, W, b):
+        Wv = self.w(W)
+        bv = None if b is None else self.w(b)
+        if Wv.dim() == 2 and x.dtype == torch.float32 and x.is_cuda and x.numel() > 0 \
+                and (bv is None or (bv.dim() == 1 and bv.dtype == torch.float32 and bv.is_contiguous())):
+            x2 = _operand(x.detach().reshape(-1, x.shape[-1]))
+            if not weight_ok(x2, Wv) and Wv.is_cuda and Wv.dtype == torch.float32:
+                # a weight outside the arena whose rows are no multiple of 4 long (W_U [d][97]): a padded copy per
+                # call (differentiable, so dW reaches the parameter); the arena stores such rows padded already
+                Wv = _operand(Wv)
+            if weight_ok(x2, Wv):
+                self._count(op)
+                return LinearF32Fn.apply(x, Wv, bv)
+        self._count(op + "_fallback")
+        y = x @ Wv
+        return y if bv is None else y + bv
+
+    def lin(self, x, W, b=None):
+        return self._lin("lin", x, W, b)
+
+    def qkv(self, x, W_Q, W_K, W_V, b_Q, b_K, b_V):
+        ps = (W_Q, W_K, W_V, b_Q, b_K, b_V)
+        if x.is_cuda and x.dtype == torch.float32 and x.numel() > 0 and all(
+                p is not None and p.dtype == torch.float32 and self.w(p) is p for p in ps) and packed_qkv(*ps):
+            H, d, dh = W_Q.shape
+            N = (H + 2 * W_K.shape[0]) * dh
+            if weight_ok(_operand(x.detach().reshape(-1, d)), W_Q.detach().as_strided((d, N), (N, 1))):
+                self._count("qkv")
+                return QKVF32Fn.apply(x, *ps)
+        self._count("qkv_fallback")
+        return TorchOps.qkv(self, x, *ps)
+
+    def o_proj(self, z, W_O, b_O):
+        Wv = self.w(W_O)
+        if Wv.dim() == 3 and Wv.is_contiguous():
+            H, dh, d = Wv.shape
+            return self._lin("o_proj", z.reshape(*z.shape[:-2], H * dh), Wv.view(H * dh, d), b_O)
+        self._count("o_proj_fallback")
+        return TorchOps.o_proj(self, z, W_O, b_O)
+
+    def mlp_in(self, x, W_in, b_in, act: str, hook_pre=None):
+        pre = self._lin("mlp_in", x, W_in, b_in)
+        if hook_pre is not None:
+            pre = hook_pre(pre)
+        return pre, act_fn(act)(pre)
+
+    def mlp_out(self, post, W_out, b_out):
+        return self._lin("mlp_out", post, W_out, b_out)
+
+    def unembed(self, x, W_U, b_U):
+        return self._lin("unembed", x, W_U, b_U)
+
+
+_OPS = None
+
+
+def get_hip32_ops(model) -> HipF32Ops:
+    """The backend for an fp32 model on a GPU; raises when the kernel library cannot be loaded (no fallback)."""
+    global _OPS
+    if model.cfg.dtype != torch.float32:
+        raise RuntimeError(f"hip32 op backend computes in fp32; the model's dtype is {model.cfg.dtype}")
+    K.lib()
+    if _OPS is None:
+        _OPS = HipF32Ops()
+    return _OPS

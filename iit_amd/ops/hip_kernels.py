@@ -32,6 +32,8 @@ GEMM_DUAL_GROUP_M = 2
 
 _SIGS = {
     "iit_gemm": [c_void_p] * 10 + [c_long] * 5 + [c_int] * 12 + [c_void_p],
+    "iit_gemm_f32": [c_void_p] * 6 + [c_long] * 4 + [c_int] * 7 + [c_void_p],
+    "iit_gemm_f32_ok": [c_void_p] * 6 + [c_long] * 4 + [c_int] * 7,
     "iit_gemm_glds": [c_void_p] * 8 + [c_long] * 5 + [c_int] * 8 + [c_void_p] * 4,
     "iit_gemm_glds_ok": [c_void_p] * 5 + [c_long] * 5 + [c_int] * 9,
     "iit_gemm_glds_sm": [c_void_p] * 8 + [c_long] * 5 + [c_int] * 8 + [c_void_p] * 3 + [c_int] + [c_void_p] * 3,
@@ -338,6 +340,54 @@ def gemm_glds(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, C2=None, bias0=None
                                   _p(cnt), int(sm), _p(bsum) if mode == 3 else None,
                                   _p(gsq) if epi == EPI_F32_STORE else None, _stream()),
            "iit_gemm_glds")
+
+
+# ------------------------------------------------------------------------------ exact-fp32 GEMM (csrc/gemm_f32.hip)
+GEMM_F32_TILES = {0: (64, 64), 1: (128, 128)}  # tile id -> (BM, BN); K-tiles of 32 / 16
+
+
+def _f32_cuda(*ts) -> bool:
+    return all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in ts)
+
+
+def gemm_f32_ok(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, bias=None, resid=None, ldr=0, tile=0, splits=1) -> bool:
+    """Whether the fp32 MFMA kernel covers this problem: fp32 GPU operands, 16-byte aligned base pointers, leading
+    dimensions that are multiples of 4 elements, ``mode`` 0..3, ``EPI_F32_STORE`` / ``_RESID`` / ``_ACC``, a tile of
+    ``GEMM_F32_TILES`` and 1..64 splits."""
+    if not _f32_cuda(A, B, C, bias, resid) or tile not in GEMM_F32_TILES:
+        return False
+    # the split workspace comes from torch's allocator (512-byte aligned): a stand-in aligned address
+    ws = 16 if splits > 1 else None
+    return bool(lib().iit_gemm_f32_ok(_p(A), _p(B), _p(C), _p(bias), _p(resid), ws, lda, ldb, ldc, ldr, M, N, K, mode,
+                                      epi, tile, splits))
+
+
+def gemm_f32_splits(M: int, N: int, K: int, tile: int = 0) -> int:
+    """Split-K factor of an fp32 GEMM: a stated policy, not a tuned table.  Enough splits that the launch has about
+    one workgroup per CU (``N_CU`` = 256), at least 128 of K per split, at most 64 splits; 1 when the output tiles
+    alone fill the chip or K is short."""
+    bm, bn = GEMM_F32_TILES[tile]
+    tiles = math.ceil(M / bm) * math.ceil(N / bn)
+    return max(1, min(N_CU // tiles, K // 128, 64))
+
+
+def gemm_f32(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, bias=None, resid=None, ldr=0, tile=0, splits=1):
+    """C = A @ B (+ epilogue) in exact fp32 on ``v_mfma_f32_16x16x4_f32`` (``csrc/gemm_f32.hip``); fp32 operands in
+    the layout of ``mode`` (``MODE_AKM`` / ``MODE_BKM`` bits), strides in elements.  ``splits > 1``: deterministic
+    split-K through a ``[splits][M][N]`` workspace allocated here with ``torch.empty`` (the caching allocator keeps
+    it alive for a capturing graph's pool, so the call is safe under ``torch.cuda.graph``).  Raises, without
+    launching, for a problem ``gemm_f32_ok`` refuses."""
+    if not gemm_f32_ok(A, B, C, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, mode=mode, epi=epi, bias=bias, resid=resid,
+                       ldr=ldr, tile=tile, splits=splits):
+        raise RuntimeError(f"iit_gemm_f32: unsupported problem M={M} N={N} K={K} lda={lda} ldb={ldb} ldc={ldc} "
+                           f"ldr={ldr} mode={mode} epi={epi} tile={tile} splits={splits} (fp32 GPU operands, 16-byte "
+                           f"aligned pointers, leading dimensions multiples of 4)")
+    if CHECK_BOUNDS:
+        _gemm_bounds("iit_gemm_f32", A, B, C, None, resid, M, N, K, lda, ldb, ldc, 0, ldr, mode)
+        _bounds("iit_gemm_f32", ("bias", bias, 1, N, N))
+    ws = torch.empty(splits * M * N, dtype=torch.float32, device=A.device) if splits > 1 else None
+    _check(lib().iit_gemm_f32(_p(A), _p(B), _p(C), _p(bias), _p(resid), _p(ws), lda, ldb, ldc, ldr, M, N, K, mode, epi,
+                              tile, splits, _stream()), "iit_gemm_f32")
 
 
 # ------------------------------------------------------------------------------ dual GEMM (csrc/gemm_dual.hip)

@@ -9,6 +9,7 @@ epochs run, the wall-clock, whether the early-stop criterion was met, and the fi
     python scripts/time_to_iia.py --model ioi-6l --engine native            # this engine (fp32, graphs)
     python scripts/time_to_iia.py --model ioi-6l --engine reference         # reference-semantics eager fp32
     python scripts/time_to_iia.py --model gpt2-small --dtype bf16 --epochs 20
+    python scripts/time_to_iia.py --model ioi-6l --fp32-backend hip32 --epochs 30   # projections on csrc/gemm_f32.hip
 """
 from __future__ import annotations
 
@@ -37,6 +38,9 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--graphs", type=int, default=1, help="1: engine default, 2: force graphs, 0: eager")
     ap.add_argument("--seed", type=int, default=0, help="torch / numpy seed (the reference uses 0)")
+    ap.add_argument("--fp32-backend", default="torch", choices=["torch", "hip32"],
+                    help="op backend of an fp32 native run, as train_ioi.py --fp32-backend")
+    ap.add_argument("--dump-epochs", default=None, help="write every epoch's (epoch, wall s, metrics) as JSON lines")
     args = ap.parse_args()
 
     from iit_amd.data.iit_dataset import IITDataset, train_test_split
@@ -55,7 +59,9 @@ def main():
         cfg.update(ioi_cfg)
     cfg.update(init_weights=True, device=str(dev), dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     ll = HookedTransformer(cfg)
-    if args.dtype == "fp32" or args.engine == "reference":
+    if args.dtype == "fp32" and args.engine == "native" and args.fp32_backend == "hip32":
+        ll.set_op_backend("hip32")
+    elif args.dtype == "fp32" or args.engine == "reference":
         ll.set_op_backend("torch")
     ds, hl = make_ioi_dataset_and_hl(args.num_samples, ll, NAMES, device=dev,
                                      label_format="onehot" if args.engine == "reference" else "index")
@@ -107,6 +113,10 @@ def main():
     if not pdist.is_main():  # only rank 0 logs epochs (and writes the record)
         pdist.destroy()
         return
+    if args.dump_epochs:
+        with open(args.dump_epochs, "w") as f:
+            for e, t, m in epochs_seen:
+                f.write(json.dumps({"epoch": e, "wall_s": round(t, 3), **{k: float(v) for k, v in m.items()}}) + "\n")
     last_epoch, _, last = epochs_seen[-1]
     converged = bool(pair._check_early_stop_condition(pair.test_metrics.metrics))
     first_100 = next((e for e, _, m in epochs_seen if m.get("val/IIA", 0) >= 100), None)
