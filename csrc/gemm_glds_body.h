@@ -330,12 +330,22 @@ struct GldsSmem {
   static constexpr int BYTES = NS * STAGE > EPI_BYTES ? NS * STAGE : EPI_BYTES;
 };
 
+// The ragged N edge (csrc/gemm_edge.hip) in one place, for the device code and the host plan alike.  Columns are
+// handled in granules of 8 (16 B of bf16): a k-major operand granule starting at column ``c`` is read from the
+// operand when ``c < N`` (it may run into the row's pad [N, pad8(N)), whose contents only reach output columns >= N,
+// which are never stored) and from the zero page otherwise; an output granule stores its first edge_valid(c, N)
+// columns.
+__host__ __device__ __forceinline__ bool edge_redirect(int c, int N) { return c >= N; }
+__host__ __device__ __forceinline__ int edge_valid(int c, int N) { return c + 8 <= N ? 8 : (c < N ? N - c : 0); }
+
 // The epilogue of an output tile, shared by the LDS-DMA kernels: the fp32 accumulators go through LDS in ECH row
 // chunks of BM / ECH rows (``write_acc(E, ch)`` stores this thread's accumulators of chunk ``ch`` into the row-major
 // [BM / ECH][EPS] fp32 tile E), then each thread owns 8 consecutive columns of a row: 16-B / 32-B vector loads of
 // bias / residual / accumulator and vector stores with the fused epilogue (bias, residual, gelu, dgelu + column sums,
 // fp32 accumulate / store + sum of squares).
-template <int BM, int BN, int EPI, int NT, int ECH, int EPS, class WriteAcc>
+// EDGE (E_BF16 / E_F32_ACC / E_F32_STORE): N need not be a tile multiple -- column granules at or beyond N are skipped,
+// the straddling one is loaded / stored element by element, and its masked columns stay out of ``gsq``.
+template <int BM, int BN, int EPI, int NT, int ECH, int EPS, bool EDGE = false, class WriteAcc>
 __device__ __forceinline__ void glds_epilogue(const G2Args& p, char* smem, const int m0, const int n0, const int lin,
                                               WriteAcc&& write_acc) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -364,8 +374,16 @@ __device__ __forceinline__ void glds_epilogue(const G2Args& p, char* smem, const
         pf[2 * k + 1] = *(const float4*)(src + 4);
       } else if constexpr (EPI == E_F32_ACC) {
         const float* src = (const float*)p.C + (long)row * p.ldc + col;
-        pf[2 * k] = *(const float4*)src;
-        pf[2 * k + 1] = *(const float4*)(src + 4);
+        if (!EDGE || edge_valid(col, p.N) == 8) {
+          pf[2 * k] = *(const float4*)src;
+          pf[2 * k + 1] = *(const float4*)(src + 4);
+        } else {
+          float t[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) t[e] = e < edge_valid(col, p.N) ? src[e] : 0.f;
+          pf[2 * k] = make_float4(t[0], t[1], t[2], t[3]);
+          pf[2 * k + 1] = make_float4(t[4], t[5], t[6], t[7]);
+        }
       } else if constexpr (PF16) {
         pb[k] = *(const bf16x8*)((const __bf16*)p.C2 + (long)row * p.ldc2 + col);
       }
@@ -384,6 +402,30 @@ __device__ __forceinline__ void glds_epilogue(const G2Args& p, char* smem, const
     {
       const float4 x = *(const float4*)(E + lr * EPS + lc), y = *(const float4*)(E + lr * EPS + lc + 4);
       v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; v[4] = y.x; v[5] = y.y; v[6] = y.z; v[7] = y.w;
+    }
+    if constexpr (EDGE) {
+      static_assert(EPI == E_BF16 || EPI == E_F32_ACC || EPI == E_F32_STORE, "edge epilogues");
+      const int nv = edge_valid(col, p.N);
+      if (nv == 0) continue;
+      if (nv < 8) {  // the granule that straddles N: element by element, nothing touched at or beyond column N
+        if constexpr (EPI == E_F32_ACC) {
+          add8v(v, pf[2 * k], pf[2 * k + 1]);
+        } else if (p.bias0) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (e < nv) v[e] += p.bias0[col + e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (e < nv) {
+            if constexpr (EPI == E_BF16) ((__bf16*)p.C)[(long)row * p.ldc + col + e] = f2bf(v[e]);
+            else ((float*)p.C)[(long)row * p.ldc + col + e] = v[e];
+            if constexpr (EPI == E_F32_STORE) {
+              if (p.gsq) sq += v[e] * v[e];
+            }
+          }
+        continue;
+      }
     }
     if constexpr (EPI == E_BF16) {
       if (p.bias0) add8(v, p.bias0 + col);
@@ -510,8 +552,11 @@ __device__ __forceinline__ void glds_epilogue(const G2Args& p, char* smem, const
 // One output tile of one GEMM problem: workgroup ``lin`` of the ``nlin`` tiles of K-split ``split`` of ``nsplit``
 // (a single-problem launch passes its block index and grid size; the dual launch in gemm_dual.hip maps its
 // workgroups onto two problems).  ``smem`` is the launch's one LDS object of at least GldsSmem<...>::BYTES.
+// EDGE (csrc/gemm_edge.hip): N is any positive number -- the last N-tile is partial.  B is k-major and staged by a
+// BSTG that reads nothing at or beyond column N (EdgeBStager); the fused sums and the epilogue skip those columns.
+// One K split only.
 template <int BM, int BN, int NS, bool AKM, bool BKM, int EPI, int NW, int BK = 64, int OCC = 1, bool LEAN = false,
-          class ASTG = void, class BSTG = void>
+          class ASTG = void, class BSTG = void, bool EDGE = false>
 __device__ __forceinline__ void gemm_glds_body(const G2Args& p, const int lin, const int nlin, const int split,
                                                const int nsplit, char* smem) {
   // ASTG / BSTG: operand stagers other than the strided-matrix one (the convolution's implicit im2col rows /
@@ -538,7 +583,8 @@ __device__ __forceinline__ void gemm_glds_body(const G2Args& p, const int lin, c
   constexpr bool TR = EPI != E_F32_ACC;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;  // wave (wm, wn) of the WMR x 2 grid
-  const int tiles_n = p.N / BN;
+  static_assert(!EDGE || (BKM && !std::is_void_v<BSTG>), "the edge variant stages its k-major B itself");
+  const int tiles_n = EDGE ? (p.N + BN - 1) / BN : p.N / BN;
   const int t = xcd_remap(lin, nlin);
   int tm, tn;
   // XCD-local order, 8-high column groups.  Whole rows of output tiles per XCD (group height 1: each activation
@@ -697,7 +743,8 @@ __device__ __forceinline__ void gemm_glds_body(const G2Args& p, const int lin, c
         float v = cs[j];
         v += __shfl_xor(v, 16);
         v += __shfl_xor(v, 32);
-        if (lane < 16) atomicAdd(p.bsum + n0 + wn * WN + j * 16 + lane, v);
+        if (lane < 16 && (!EDGE || n0 + wn * WN + j * 16 + lane < p.N))
+          atomicAdd(p.bsum + n0 + wn * WN + j * 16 + lane, v);
       }
     }
   }
@@ -775,7 +822,7 @@ __device__ __forceinline__ void gemm_glds_body(const G2Args& p, const int lin, c
     }
   }
   // ---------------------------------------------------------------- epilogue via LDS (ECH row chunks)
-  glds_epilogue<BM, BN, EPI, NT, ECH, SM::EPS>(p, smem, m0, n0, lin, [&](float* E, int ch) {
+  glds_epilogue<BM, BN, EPI, NT, ECH, SM::EPS, EDGE>(p, smem, m0, n0, lin, [&](float* E, int ch) {
     if (wm / (WMR / ECH) == ch) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)

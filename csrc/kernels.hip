@@ -1078,6 +1078,58 @@ IIT_EXPORT int iit_ce_bwd(const float* logits, long ld, const long* labels, cons
   return hipGetLastError();
 }
 
+// The bf16-only form of ce_bwd, for a gradient whose one reader is the unembed backward (which takes bf16 operands):
+// no fp32 [rows][vocab] image is written at all.  Each thread owns 8 consecutive columns of a row -- two 16-B loads
+// of the logits where the row is 16-B aligned and the 8 columns lie inside the vocabulary, one 16-B store -- and the
+// values are those of ce_bwd_kernel's ``out16`` bit for bit (same expression, same rounding).  ld_out % 8 == 0;
+// pad columns [V, ld_out) are zeroed.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ce_bwd16_kernel(const float* __restrict__ logits, long ld,
+                                                       const long* __restrict__ labels, const float* __restrict__ lse,
+                                                       const float* __restrict__ gscale, float inv_rows,
+                                                       __bf16* __restrict__ out16, long ld_out, int V) {
+  const int row = blockIdx.y;
+  const int c0 = (blockIdx.x * 256 + threadIdx.x) * 8;
+  if (c0 >= ld_out) return;
+  const float* x = logits + (long)row * ld;
+  const float l = lse[row], gs = gscale[0];
+  const long lab = labels[row];
+  float v[8];
+  if (VEC && c0 + 8 <= V) {
+    const float4 a = *(const float4*)(x + c0), b = *(const float4*)(x + c0 + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = c0 + e < V ? x[c0 + e] : 0.f;
+  }
+  bf16x8 o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int i = c0 + e;
+    float g = 0.f;
+    if (i < V) {
+      const float p = __expf(v[e] - l);
+      g = (p - (i == lab ? 1.f : 0.f)) * gs * inv_rows;
+    }
+    o[e] = f2bf(g);
+  }
+  *(bf16x8*)(out16 + (long)row * ld_out + c0) = o;
+}
+
+IIT_EXPORT int iit_ce_bwd16(const float* logits, long ld, const long* labels, const float* lse, const float* gscale,
+                            float inv_rows, void* out16, long ld_out, int R, int V, void* stream) {
+  if (R <= 0 || V <= 0 || ld < V || ld_out < V || ld_out % 8 || ((uintptr_t)out16 & 15)) return (int)hipErrorInvalidValue;
+  dim3 grid((unsigned)((ld_out / 8 + 255) / 256), R);
+  const bool vec = (((uintptr_t)logits | (uintptr_t)(ld * 4)) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(ce_bwd16_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, logits, ld, labels, lse, gscale,
+                       inv_rows, (__bf16*)out16, ld_out, V);
+  else
+    hipLaunchKernelGGL(ce_bwd16_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, logits, ld, labels, lse,
+                       gscale, inv_rows, (__bf16*)out16, ld_out, V);
+  return hipGetLastError();
+}
+
 // ============================================================================ optimizer
 // partial sums of g^2 per block (grid-stride over float4)
 // Stage 1 of the fused clip+Adam: per-block partial sums of g^2 (skipped when clip == 0) and the

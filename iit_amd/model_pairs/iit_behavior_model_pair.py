@@ -62,7 +62,8 @@ class IITBehaviorModelPair(IITModelPair):
         output = self.ll_forward(base_x)
         if output.dim() > 1 and output.shape[0] == 1:
             return loss_fn(output, base_y)
-        return loss_fn(output.squeeze(), base_y)
+        # (a squeeze that removes nothing would still hand the loss a new view, without the tags the logits carry)
+        return loss_fn(output.squeeze() if 1 in output.shape else output, base_y)
 
     def step_on_loss(self, loss: Tensor, optimizer) -> None:
         optimizer.zero_grad()

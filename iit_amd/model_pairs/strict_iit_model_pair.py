@@ -48,7 +48,8 @@ class StrictIITModelPair(IITBehaviorModelPair):
             out = self.ll_intervened_forward(base_x, [ll_node])
         if out.dim() > 1 and out.shape[0] == 1:
             return loss_fn(out, base_y)
-        return loss_fn(out.squeeze(), base_y)
+        # (a squeeze that removes nothing would still hand the loss a new view, without the tags the logits carry)
+        return loss_fn(out.squeeze() if 1 in out.shape else out, base_y)
 
     def run_train_step(self, base_input, ablation_input, loss_fn, optimizer):
         args = self.training_args

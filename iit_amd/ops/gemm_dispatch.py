@@ -380,6 +380,16 @@ def _candidates_plain(A, B, C, C2, M, N, Kd, lda, ldb, ldc, mode, epi, bias0, bi
                         K_.gemm_glds(A, B, c, M=M, N=N, K=Kd, lda=lda, ldb=ldb, ldc=ldc, mode=mode, epi=epi,  # noqa
                                      bias0=bias0, resid=resid, ldr=ldr, tile=t, splits=sp, reduce=True, bsum=bs,
                                      gsq=sq)
+        # a ragged N (the vocabulary-sized unembed forward and weight gradient) whole, in ONE launch on the
+        # edge-capable tiles (csrc/gemm_edge.hip) -- a candidate beside the bulk + tail split of _ragged_split
+        if N % 128 and mode in (2, 3) and C2 is None and resid is None and aux is None and bias1 is None \
+                and csum_box is None:
+            for tile in K_.GLDS_EDGE_TILES:
+                if K_.gemm_glds_edge_ok(A, B, C, M=M, N=N, K=Kd, lda=lda, ldb=ldb, ldc=ldc, mode=mode, epi=epi,
+                                        bias0=bias0, tile=tile):
+                    calls[f"glds{tile}e"] = lambda c=C, c2=C2, c3=None, t=tile, bs=None, sq=None: \
+                        K_.gemm_glds_edge(A, B, c, M=M, N=N, K=Kd, lda=lda, ldb=ldb, ldc=ldc, mode=mode, epi=epi,  # noqa
+                                          bias0=bias0, tile=t, bsum=bs, gsq=sq)
     if epi in _BLAS16_EPIS:
         calls["blas16"] = lambda c=C, c2=C2, c3=None: _blas16(A, B, c, M, N, Kd, lda, ldb, ldc, mode, epi,  # noqa
                                                              bias0, resid, ldr)
@@ -447,6 +457,20 @@ def _shift(t, off: int):
 RAGGED = {}  # ragged problem key -> (split wins, whole time, [bulk time, tail time])
 
 
+EDGE: Dict[Tuple, str] = {}  # ragged problem key -> "glds{tile}e" ("" = none): the shipped whole-problem edge choice
+
+
+def _edge_whole(rkey) -> Optional[str]:
+    """The shipped choice ``glds{tile}e`` for a ragged problem that the table otherwise splits ("edge" section of the
+    decision table: measured faster than bulk + tail, profiles/loss_tail_ab.txt), or None."""
+    name = EDGE.get(rkey)
+    if name is None:
+        name = EDGE[rkey] = _edge_table().get(repr(rkey), "")
+    if not name or re.fullmatch(r"glds\d+e", name) is None or _excluded(name, rkey):
+        return None
+    return name
+
+
 def _ragged_split(A, B, C, *, M, N, K, lda, ldb, mode, epi, C2, bias0, resid, aux, bsum=None, gsq=None):
     """Problem pieces ``[kwargs, ...]`` for a GEMM whose N (any column-wise epilogue) or K (fp32 accumulate) is
     large but not tile-aligned: a bulk of N // 128 * 128 columns (resp. K // 1024 * 1024 reduction steps, so
@@ -496,7 +520,9 @@ def gemm(A, B, C, *, M, N, K: int, lda, ldb, ldc, mode=0, epi=0, C2=None, C3=Non
     epilogue, or as a pass over ``C`` after any other implementation; not part of the decision either.
 
     Ragged problems (the vocabulary-sized unembed GEMMs: N or K = 50257) are split into a tile-aligned bulk, which
-    the LDS-DMA kernel can serve, and a narrow tail (see :func:`_ragged_split`).
+    the LDS-DMA kernel can serve, and a narrow tail (see :func:`_ragged_split`) -- or, for a ragged N with a k-major
+    B, run whole on the ragged-N variant of that kernel (``glds{tile}e``, csrc/gemm_edge.hip): a candidate of the
+    whole problem when the choice is measured, the table's "edge" section when it is shipped.
 
     Returns the name of the implementation that ran when the choice was measured (else None)."""
     Kd = K
@@ -533,6 +559,16 @@ def gemm(A, B, C, *, M, N, K: int, lda, ldb, ldc, mode=0, epi=0, C2=None, C3=Non
                 split = RAGGED[rkey] = (None not in pieces and whole is not None and sum(pieces) < whole,
                                         whole, pieces)
             if split is not None and split[0]:
+                # bulk + tail, or -- where the table's "edge" section names an edge-capable tile for this problem -- the
+                # whole ragged problem in ONE launch of the ragged-N kernel (csrc/gemm_edge.hip).  The split stays the
+                # fallback (no entry, an operand the variant does not cover) and the IIT_GEMM_TAIL_LIBRARY path.
+                edge = None if _TAIL_LIBRARY else _edge_whole(rkey)
+                if edge is not None and C2 is None and resid is None and aux is None and bias1 is None:
+                    tile = int(edge[4:-1])
+                    ekw = dict(M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, mode=mode, epi=epi, bias0=bias0, tile=tile)
+                    if K_.gemm_glds_edge_ok(A, B, C, **ekw):
+                        K_.gemm_glds_edge(A, B, C, bsum=bsum, gsq=gsq, **ekw)
+                        return edge
                 choice = run(bulk)
                 run(tail, tail=True)
                 return choice
@@ -773,6 +809,13 @@ def _parse_dual(name: str):
 _TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned", "gemm_decisions_gfx950.json")
 _TABLE = None
 _RAGGED_TABLE: Dict[str, bool] = {}
+_EDGE_TABLE: Dict[str, str] = {}
+
+
+def _edge_table() -> Dict[str, str]:
+    """Shipped whole-problem edge choices (``"edge"`` section of the table) for ragged problems."""
+    _table()
+    return _EDGE_TABLE
 
 
 def _ragged_table() -> Dict[str, bool]:
@@ -786,6 +829,7 @@ def _table() -> Dict[str, str]:
     if _TABLE is None:
         _TABLE = {}
         _RAGGED_TABLE.clear()
+        _EDGE_TABLE.clear()
         path = os.environ.get("IIT_GEMM_TABLE", _TABLE_PATH)
         if path != "0" and os.path.exists(path) and torch.cuda.is_available():
             import json
@@ -796,6 +840,7 @@ def _table() -> Dict[str, str]:
                 if data.get("arch") == arch:  # decisions measured on this GPU architecture only
                     _TABLE = dict(data.get("decisions", {}))
                     _RAGGED_TABLE.update({k: bool(v) for k, v in data.get("ragged", {}).items()})
+                    _EDGE_TABLE.update({k: str(v) for k, v in data.get("edge", {}).items()})
             except (OSError, ValueError) as e:  # pragma: no cover - a corrupt table only costs autotuning
                 print(f"[iit] GEMM decision table not loaded ({e})")
     return _TABLE
@@ -840,7 +885,8 @@ def export_table(path: str) -> int:
         if torch.cuda.is_available() else None
     with open(path, "w") as f:
         json.dump({"arch": arch, "device": torch.cuda.get_device_name(0) if torch.cuda.is_available() else None,
-                   "decisions": dec, "ragged": ragged}, f, indent=0, sort_keys=True)
+                   "decisions": dec, "ragged": ragged, "edge": {repr(k): v for k, v in EDGE.items() if v}}, f,
+                  indent=0, sort_keys=True)
     return len(dec) + len(ragged)
 
 

@@ -61,6 +61,10 @@ _SIGS = {
     "iit_ce_fwd": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "iit_ce_bwd": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_long, c_int, c_int, c_int,
                    c_void_p, c_void_p],
+    "iit_gemm_glds_edge_ok": [c_void_p] * 4 + [c_long] * 3 + [c_int] * 6,
+    "iit_gemm_glds_edge": [c_void_p] * 4 + [c_long] * 3 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p],
+    "iit_gemm_edge_plan": [c_int, c_int, c_long, c_int, c_int, c_void_p],
+    "iit_ce_bwd16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_long, c_int, c_int, c_void_p],
     "iit_adam_flat": [c_void_p] * 6 + [c_int, c_void_p, c_int] + [c_float] * 6 + [c_void_p] * 3
                      + [c_void_p, c_int, c_void_p, c_void_p],
     "iit_sumsq_2d": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p],
@@ -340,6 +344,45 @@ def gemm_glds(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, C2=None, bias0=None
                                   _p(cnt), int(sm), _p(bsum) if mode == 3 else None,
                                   _p(gsq) if epi == EPI_F32_STORE else None, _stream()),
            "iit_gemm_glds")
+
+
+# ------------------------------------------------------------------------------ ragged-N LDS-DMA GEMM (csrc/gemm_edge.hip)
+GLDS_EDGE_TILES = (0, 7, 25)  # the edge-capable tiles, under their ids in GLDS_TILES
+
+
+def gemm_glds_edge_ok(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, bias0=None, tile=25) -> bool:
+    """Whether the ragged-N variant of the LDS-DMA kernel covers this problem: B k-major (mode 2 with a bf16 / fp32
+    store / fp32 accumulate epilogue, mode 3 with an fp32 store / accumulate), any N > 0, M and K tile multiples,
+    rows of B and C at least ``pad8(N)`` long."""
+    if any(t is None or not t.is_cuda or t.dtype != torch.bfloat16 for t in (A, B)):
+        return False
+    return bool(lib().iit_gemm_glds_edge_ok(_p(A), _p(B), _p(C), _p(bias0), lda, ldb, ldc, M, N, K, mode, epi, tile))
+
+
+def gemm_glds_edge(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, bias0=None, tile=25, store_mode=None, bsum=None,
+                   gsq=None):
+    """``gemm_glds`` for a problem whose N is no multiple of the tile, in one launch: columns >= N are neither read
+    past a row's ``pad8(N)`` columns, nor stored, nor summed into ``bsum`` / ``gsq`` (see csrc/gemm_edge.hip)."""
+    if CHECK_BOUNDS:
+        a = ("A", A, K, M, lda) if mode & MODE_AKM else ("A", A, M, K, lda)
+        _bounds("iit_gemm_glds_edge", a, ("B", B, K, (N + 7) // 8 * 8, ldb), ("C", C, M, N, ldc),
+                ("bias0", bias0, 1, N, N), ("bsum", bsum, 1, N, N))
+    sm = GLDS_STORE_MODE if store_mode is None else store_mode
+    gm = int(os.environ.get("IIT_GEMM_GROUP_M", str(GEMM_GROUP_M)) or 0)
+    _check(lib().iit_gemm_glds_edge(_p(A), _p(B), _p(C), _p(bias0), lda, ldb, ldc, M, N, K, mode, epi, tile, int(sm),
+                                    _p(bsum) if mode == 3 else None, _p(gsq) if epi == EPI_F32_STORE else None, gm,
+                                    _stream()), "iit_gemm_glds_edge")
+
+
+def gemm_edge_plan(rows: int, N: int, ld: int, elem: int, tile: int) -> Optional[dict]:
+    """The N-edge arithmetic of the kernels, on the host (no device call): for an operand / output of ``rows`` rows
+    with row stride ``ld`` elements of ``elem`` bytes -- N-tiles, granules (8 columns) per row that are read or
+    stored, granules redirected to the zero page or skipped, valid columns of the straddling granule, one past the
+    last byte touched and one past the last valid byte.  None when the tile or the shape is not covered."""
+    out = (ctypes.c_long * 6)()
+    if lib().iit_gemm_edge_plan(rows, N, ld, elem, tile, ctypes.cast(out, c_void_p)) != 0:
+        return None
+    return dict(zip(("tiles_n", "used", "redirected", "straddle", "last_byte", "valid_bytes"), list(out)))
 
 
 # ------------------------------------------------------------------------------ exact-fp32 GEMM (csrc/gemm_f32.hip)
@@ -1038,6 +1081,16 @@ def ce_bwd(logits, ld, labels, lse, gscale, inv_rows, out, ld_out, R, V, out16=N
         _bounds("ce_bwd", ("logits", logits, R, V, ld), ("out", out, R, V, ld_out))
     _check(lib().iit_ce_bwd(_p(logits), ld, _p(labels), _p(lse), _p(gscale), inv_rows, _p(out), ld_out, R, V,
                             int(out.dtype == torch.bfloat16), _p(out16), _stream()), "ce_bwd")
+
+
+def ce_bwd16(logits, ld, labels, lse, gscale, inv_rows, out16, ld_out, R, V):
+    """``ce_bwd`` writing only the bf16 gradient ``out16`` [R][ld_out] (ld_out % 8 == 0, pad columns zeroed): the
+    operand of the unembed backward GEMMs, bit for bit the ``out16`` of :func:`ce_bwd`."""
+    assert logits.dtype == torch.float32 and out16.dtype == torch.bfloat16 and gscale.dtype == torch.float32
+    if CHECK_BOUNDS:
+        _bounds("ce_bwd16", ("logits", logits, R, V, ld), ("out16", out16, R, ld_out, ld_out))
+    _check(lib().iit_ce_bwd16(_p(logits), ld, _p(labels), _p(lse), _p(gscale), inv_rows, _p(out16), ld_out, R, V,
+                              _stream()), "ce_bwd16")
 
 
 def colsum_accum(x, ld, out, T, N):

@@ -1110,6 +1110,26 @@ class LinearFn(Function):
         return dx, None, None, None, None, gres, None
 
 
+class UnembedFn(LinearFn):
+    """The fp32-logits unembed with a second, data-free output: a bf16 ``handle`` of the logits' shape (one element,
+    expanded) that exists only to carry a gradient.  A loss that computes its logits gradient directly in bf16 --
+    the dtype this backward's GEMMs read -- takes the handle as its autograd input instead of the logits
+    (:func:`cross_entropy`), so no fp32 [rows][vocab] gradient is written.  Gradients arriving through the logits
+    themselves (any other consumer) are handled as before and summed with the handle's."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, w, ldw):
+        res = LinearFn.forward(ctx, x, W, b, w, ldw, None, "f32")
+        handle = torch.empty(1, dtype=BF16, device=res.device).expand(res.shape)
+        return res, handle
+
+    @staticmethod
+    def backward(ctx, gy, gh=None):
+        if gh is not None:
+            gy = gh if gy is None else gy.float() + gh.float()
+        return LinearFn.backward(ctx, gy)[:5]
+
+
 class MLPInFn(Function):
     """(pre, post) = (x @ W_in + b_in, gelu_new(pre)) in one GEMM epilogue."""
 
@@ -1259,10 +1279,14 @@ class MLPOutGeluFn(Function):
 
 
 class CrossEntropyFn(Function):
-    """mean_r CE(logits[r], labels[r]) over fp32 logits with any row stride; fused fwd stats + bwd."""
+    """mean_r CE(logits[r], labels[r]) over fp32 logits with any row stride; fused fwd stats + bwd.
+
+    ``handle`` (optional): the bf16 gradient handle of the logits' producer (:class:`UnembedFn`).  The backward then
+    writes only the bf16 gradient, returned as the handle's gradient; the logits come in detached and no fp32
+    [rows][vocab] gradient exists."""
 
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, handle=None):
         ctx.set_materialize_grads(False)
         R, V = logits.shape
         if logits.stride(1) != 1:
@@ -1273,29 +1297,54 @@ class CrossEntropyFn(Function):
         lab = labels.contiguous()
         K.ce_fwd(logits, ld, lab, loss, lse, None, R, V)
         ctx.save_for_backward(logits, lab, lse)
+        ctx.only16 = handle is not None
         return loss.mean()
 
     @staticmethod
     def backward(ctx, g):
         if g is None:
-            return None, None
+            return None, None, None
         logits, lab, lse = ctx.saved_tensors
         R, V = logits.shape
         ld = logits.stride(0)
         ldo = _pad8(V)
+        buf16 = torch.empty(R, ldo, dtype=BF16, device=logits.device)
+        gs = g.reshape(1).float().contiguous()
+        if ctx.only16:
+            K.ce_bwd16(logits, ld, lab, lse, gs, 1.0 / R, buf16, ldo, R, V)
+            return None, None, buf16[:, :V]
         # fp32 (autograd casts a gradient to its input's dtype anyway) plus, in the same pass, the bf16 twin with
         # the same padded row stride that the unembed backward GEMMs read
         buf = torch.empty(R, ldo, dtype=F32, device=logits.device)
-        buf16 = torch.empty(R, ldo, dtype=BF16, device=logits.device)
-        gs = g.reshape(1).float().contiguous()
         K.ce_bwd(logits, ld, lab, lse, gs, 1.0 / R, buf, ldo, R, V, out16=buf16)
         res = buf[:, :V]
         _set_bf16_twin(res, buf16[:, :V])
-        return res, None
+        return res, None, None
+
+
+def _grad16_handle(logits: torch.Tensor) -> Optional[torch.Tensor]:
+    """The bf16 gradient handle tagged on ``logits`` by :meth:`HipOps.unembed`, when a bf16-only gradient is exact
+    for every reader: the tag matches the tensor's storage and version (as the bf16 twin's does), autograd is
+    recording, and nothing observes the fp32 gradient of the logits themselves -- no tensor hook, no ``retain_grad``.
+    Any other autograd consumer of the logits keeps working: its fp32 gradient and the handle's bf16 one are summed
+    by the producer's backward.  ``IIT_CE_BF16_ONLY=0`` disables."""
+    tag = getattr(logits, "_iit_grad16", None)
+    if tag is None or tag[0] != logits.data_ptr() or tag[1] != logits._version or tag[2].shape != logits.shape:
+        return None
+    if not (torch.is_grad_enabled() and tag[2].requires_grad) or logits._backward_hooks or logits.retains_grad:
+        return None
+    if os.environ.get("IIT_CE_BF16_ONLY", "1") == "0":
+        return None
+    return tag[2]
 
 
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    return CrossEntropyFn.apply(logits.float(), labels)
+    logits = logits.float()
+    handle = _grad16_handle(logits) if logits.dim() == 2 else None
+    if handle is not None:
+        logits._iit_grad16 = None  # one bf16 gradient per handle: a second loss on these logits takes the fp32 path
+        return CrossEntropyFn.apply(logits.detach(), labels, handle)
+    return CrossEntropyFn.apply(logits, labels)
 
 
 # ============================================================================ paired (source + base) rows
@@ -1834,7 +1883,11 @@ class HipOps(TorchOps):
     # -- unembed -------------------------------------------------------------------------
     def unembed(self, x, W_U, b_U):
         sh = self.shadow
-        return LinearFn.apply(x, W_U, b_U, sh.U, sh.Vp, None, "f32")
+        if sh.U is None:  # a raw null operand would fault on the GPU
+            raise RuntimeError("unembed before begin_forward(): the bf16 shadow of W_U is not bound")
+        logits, handle = UnembedFn.apply(x, W_U, b_U, sh.U, sh.Vp)
+        logits._iit_grad16 = (logits.data_ptr(), logits._version, handle)
+        return logits
 
     def unembed_argmax(self, x, W_U, b_U, chunk: int = 8192):
         sh = self.shadow
