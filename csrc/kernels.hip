@@ -985,7 +985,7 @@ __device__ __forceinline__ void online_add(float& m, float& s, int& mi, float v,
     s = s * __expf(m - v) + 1.f;
     m = v;
     mi = i;
-  } else {
+  } else if (v != -INFINITY) {  // a masked logit adds nothing; with m still -inf, v - m would be NaN (NaN logits still poison s)
     s += __expf(v - m);
   }
 }
