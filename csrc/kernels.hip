@@ -1,7 +1,6 @@
 // Non-GEMM kernels of the iit_amd engine for gfx950 (MI355X).  All wave64-native.
 //
 //  embed_pos_fwd / embed_bwd / pos_bwd     token+position embedding (fp32 residual stream)
-//  ln_fwd / ln_bwd                          LN / LNPre, one wave per row, fp32 stats
 //  attn_small_fwd / attn_small_bwd          causal attention for S <= 64, dh <= 128, one
 //                                           workgroup per (batch, head); per-head splice of
 //                                           hook_z inside the kernel (patched heads copy the
@@ -135,678 +134,6 @@ IIT_EXPORT int iit_embed_pos_bwd(const long* tok, const float* g, float* dWE, fl
       hipLaunchKernelGGL(pos_bwd_kernel, dim3(S, (d + 255) / 256), dim3(256), 0, st, g, dWpos, B, S, d);
     else
       hipLaunchKernelGGL(pos_bwd_scalar_kernel, dim3(S), dim3(256), 0, st, g, dWpos, B, S, d);
-  }
-  return hipGetLastError();
-}
-
-// ============================================================================ layer norm
-// Row select: the interchange splice of whole positions of an LN output inside the LN kernel itself (a paired
-// source+base forward, iit_amd/models/bert.py forward_paired: MQNLI's ``hook_normalized_resid_post`` position
-// sites).  Rows [0, Tb) are the base rows, [Tb, 2 Tb) the source rows at the same (batch, position); a base row
-// whose position s has bit s of ``mask`` set normalises the SOURCE row instead (out[idx] = src[idx] for whole
-// rows), and in the backward the same base rows get no gradient (the spliced slice is a constant).  mask == 0:
-// plain LN.
-struct RowSel {
-  unsigned long long mask;
-  int S;
-  int Tb;
-};
-
-__device__ __forceinline__ bool sel_hit(const RowSel& sel, int row) {
-  return sel.mask != 0ull && row < sel.Tb && ((sel.mask >> (row % sel.S)) & 1ull);
-}
-
-// One wave per row; each lane owns V4 float4 column groups (c4 = lane + 64*i), so every load is a 16-B
-// vector and a wave instruction moves 1 KB (fp32) / 512 B (bf16).  Requires d % 4 == 0 and 16-B aligned
-// rows; the scalar kernels below cover everything else.  Stats in fp32.
-template <int V4>
-__global__ __launch_bounds__(256) void ln_fwd_vec_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                         const float* __restrict__ b, __bf16* __restrict__ y,
-                                                         float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                         int T, int d, float eps, RowSel sel,
-                                                         float* __restrict__ y32 = nullptr) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= T) return;
-  const int d4 = d >> 2;
-  const int xrow = sel_hit(sel, row) ? row + sel.Tb : row;
-  const float4* xr = (const float4*)(x + (long)xrow * d);
-  float4 v[V4];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < V4; ++i) {
-    const int c = lane + i * 64;
-    v[i] = c < d4 ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-  }
-  const float mu = wave_sum(s) / d;
-  float s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < V4; ++i) {
-    const int c = lane + i * 64;
-    if (c < d4) {
-      v[i].x -= mu; v[i].y -= mu; v[i].z -= mu; v[i].w -= mu;
-      s2 += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
-    }
-  }
-  const float rstd = rsqrtf(wave_sum(s2) / d + eps);
-  bf16x4* yr = (bf16x4*)(y + (long)row * d);
-#pragma unroll
-  for (int i = 0; i < V4; ++i) {
-    const int c = lane + i * 64;
-    if (c < d4) {
-      float4 o = make_float4(v[i].x * rstd, v[i].y * rstd, v[i].z * rstd, v[i].w * rstd);
-      if (w) {
-        const float4 ww = ((const float4*)w)[c], bb = ((const float4*)b)[c];
-        o = make_float4(o.x * ww.x + bb.x, o.y * ww.y + bb.y, o.z * ww.z + bb.z, o.w * ww.w + bb.w);
-      }
-      bf16x4 ob = {f2bf(o.x), f2bf(o.y), f2bf(o.z), f2bf(o.w)};
-      yr[c] = ob;
-      if (y32)  // the fp32 twin of the rounded output (a post-norm block's residual operand: no separate cast pass)
-        ((float4*)(y32 + (long)row * d))[c] = make_float4(bf2f(ob[0]), bf2f(ob[1]), bf2f(ob[2]), bf2f(ob[3]));
-    }
-  }
-  if (lane == 0) {
-    mean_out[row] = mu;
-    rstd_out[row] = rstd;
-  }
-}
-
-// scalar fallback: y = (x - mean) * rstd  (* w + b);   one wave per row, up to VPL floats per lane
-template <int VPL>
-__global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                     const float* __restrict__ b, __bf16* __restrict__ y,
-                                                     float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                     int T, int d, float eps, RowSel sel) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= T) return;
-  const float* xr = x + (long)(sel_hit(sel, row) ? row + sel.Tb : row) * d;
-  float v[VPL];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int c = lane + i * 64;
-    v[i] = c < d ? xr[c] : 0.f;
-    s += v[i];
-  }
-  const float mu = wave_sum(s) / d;
-  float s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int c = lane + i * 64;
-    const float z = c < d ? v[i] - mu : 0.f;
-    v[i] = z;
-    s2 += z * z;
-  }
-  const float rstd = rsqrtf(wave_sum(s2) / d + eps);
-  __bf16* yr = y + (long)row * d;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int c = lane + i * 64;
-    if (c < d) {
-      float o = v[i] * rstd;
-      if (w) o = o * w[c] + b[c];
-      yr[c] = f2bf(o);
-    }
-  }
-  if (lane == 0) {
-    mean_out[row] = mu;
-    rstd_out[row] = rstd;
-  }
-}
-
-static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-IIT_EXPORT int iit_ln_fwd_sel(const float* x, const float* w, const float* b, void* y, float* mean, float* rstd,
-                              int T, int d, float eps, unsigned long long pos_mask, int S, int Tb, void* stream);
-
-IIT_EXPORT int iit_ln_fwd(const float* x, const float* w, const float* b, void* y, float* mean, float* rstd, int T,
-                          int d, float eps, void* stream) {
-  return iit_ln_fwd_sel(x, w, b, y, mean, rstd, T, d, eps, 0ull, 1, 0, stream);
-}
-
-// iit_ln_fwd that also writes ``y32`` = fp32(y) (vector layout only: d % 4 == 0, d <= 4096, 16-B aligned rows)
-IIT_EXPORT int iit_ln_fwd_twin(const float* x, const float* w, const float* b, void* y, float* y32, float* mean,
-                               float* rstd, int T, int d, float eps, void* stream) {
-  const bool vec = d % 4 == 0 && d <= 4096 && aligned16(x) && (((uintptr_t)y) & 7) == 0 && aligned16(y32) &&
-                   (!w || (aligned16(w) && aligned16(b)));
-  if (!vec) return (int)hipErrorInvalidValue;
-  const RowSel sel{0ull, 1, 0};
-  dim3 grid((T + 3) / 4), block(256);
-  hipStream_t s = (hipStream_t)stream;
-#define LNT(V) hipLaunchKernelGGL((ln_fwd_vec_kernel<V>), grid, block, 0, s, x, w, b, (__bf16*)y, mean, rstd, T, d, eps, sel, y32)
-  const int v4 = (d / 4 + 63) / 64;
-  if (v4 <= 1) LNT(1); else if (v4 <= 2) LNT(2); else if (v4 <= 3) LNT(3); else if (v4 <= 4) LNT(4);
-  else if (v4 <= 6) LNT(6); else if (v4 <= 8) LNT(8); else if (v4 <= 12) LNT(12); else LNT(16);
-#undef LNT
-  return hipGetLastError();
-}
-
-// ``pos_mask`` (RowSel): base rows [0, Tb) at positions with their bit set normalise the source row row + Tb
-IIT_EXPORT int iit_ln_fwd_sel(const float* x, const float* w, const float* b, void* y, float* mean, float* rstd,
-                              int T, int d, float eps, unsigned long long pos_mask, int S, int Tb, void* stream) {
-  const RowSel sel{pos_mask, S > 0 ? S : 1, Tb};
-  if (pos_mask && (S <= 0 || S > 64 || 2 * (long)Tb > T)) return (int)hipErrorInvalidValue;
-  dim3 grid((T + 3) / 4), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec = d % 4 == 0 && aligned16(x) && (((uintptr_t)y) & 7) == 0 && (!w || (aligned16(w) && aligned16(b)));
-  if (vec && d <= 4096) {
-#define LNF(V) hipLaunchKernelGGL((ln_fwd_vec_kernel<V>), grid, block, 0, s, x, w, b, (__bf16*)y, mean, rstd, T, d, eps, sel)
-    const int v4 = (d / 4 + 63) / 64;
-    if (v4 <= 1) LNF(1); else if (v4 <= 2) LNF(2); else if (v4 <= 3) LNF(3); else if (v4 <= 4) LNF(4);
-    else if (v4 <= 6) LNF(6); else if (v4 <= 8) LNF(8); else if (v4 <= 12) LNF(12); else LNF(16);
-#undef LNF
-    return hipGetLastError();
-  }
-  if (d <= 256) hipLaunchKernelGGL((ln_fwd_kernel<4>), grid, block, 0, s, x, w, b, (__bf16*)y, mean, rstd, T, d, eps, sel);
-  else if (d <= 1024) hipLaunchKernelGGL((ln_fwd_kernel<16>), grid, block, 0, s, x, w, b, (__bf16*)y, mean, rstd, T, d, eps, sel);
-  else if (d <= 2048) hipLaunchKernelGGL((ln_fwd_kernel<32>), grid, block, 0, s, x, w, b, (__bf16*)y, mean, rstd, T, d, eps, sel);
-  else if (d <= 4096) hipLaunchKernelGGL((ln_fwd_kernel<64>), grid, block, 0, s, x, w, b, (__bf16*)y, mean, rstd, T, d, eps, sel);
-  else return (int)hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
-// dx = rstd * (g - mean(g) - xhat * mean(g * xhat)) (+ dres),  g = dy * w.
-// ``dres`` (nullable) is the residual stream's skip-connection gradient: fusing it here saves autograd's
-// separate gradient-sum pass over the fp32 residual.  ``dx16`` (nullable) receives a bf16 copy of dx: the
-// next backward GEMMs (W_O / W_out dX and dW) read bf16, so the cast rides along with this pass.
-// The affine gradients dw/db are NOT done here (see ln_dwdb_kernel: per-block partial sums, few atomics).
-// XH16: ``x`` is the forward's bf16 output xhat of a norm without affine parameters (LNPre): 2 bytes per element
-// instead of the fp32 input, and no mean
-template <int V4, bool DY_F32, bool XH16 = false>
-__global__ __launch_bounds__(256) void ln_bwd_vec_kernel(const void* __restrict__ dy_, const float* __restrict__ x,
-                                                         const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                         const float* __restrict__ w, float* __restrict__ dx,
-                                                         const float* __restrict__ dres, __bf16* __restrict__ dx16,
-                                                         int T, int d, int accumulate, RowSel sel) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= T) return;
-  const int d4 = d >> 2;
-  const bool dead = sel_hit(sel, row);  // a spliced row: its output came from the source row (no gradient here)
-  const float mu = mean[row], rs = rstd[row];
-  float4 g[V4], xh[V4];
-  float sg = 0.f, sgx = 0.f;
-#pragma unroll
-  for (int i = 0; i < V4; ++i) {
-    const int c = lane + i * 64;
-    float4 dy = make_float4(0.f, 0.f, 0.f, 0.f), xv = dy;
-    if (c < d4 && !dead) {
-      if (DY_F32) {
-        dy = ((const float4*)dy_)[(long)row * d4 + c];
-      } else {
-        const bf16x4 t = ((const bf16x4*)dy_)[(long)row * d4 + c];
-        dy = make_float4(bf2f(t[0]), bf2f(t[1]), bf2f(t[2]), bf2f(t[3]));
-      }
-      if constexpr (XH16) {
-        const bf16x4 t = ((const bf16x4*)x)[(long)row * d4 + c];
-        xv = make_float4(bf2f(t[0]), bf2f(t[1]), bf2f(t[2]), bf2f(t[3]));
-      } else {
-        const float4 xx = ((const float4*)x)[(long)row * d4 + c];
-        xv = make_float4((xx.x - mu) * rs, (xx.y - mu) * rs, (xx.z - mu) * rs, (xx.w - mu) * rs);
-      }
-      if (w) {
-        const float4 ww = ((const float4*)w)[c];
-        dy.x *= ww.x; dy.y *= ww.y; dy.z *= ww.z; dy.w *= ww.w;
-      }
-    }
-    g[i] = dy;
-    xh[i] = xv;
-    sg += (dy.x + dy.y) + (dy.z + dy.w);
-    sgx += (dy.x * xv.x + dy.y * xv.y) + (dy.z * xv.z + dy.w * xv.w);
-  }
-  sg = wave_sum(sg) / d;
-  sgx = wave_sum(sgx) / d;
-#pragma unroll
-  for (int i = 0; i < V4; ++i) {
-    const int c = lane + i * 64;
-    if (c < d4) {
-      float4 o = make_float4(rs * (g[i].x - sg - xh[i].x * sgx), rs * (g[i].y - sg - xh[i].y * sgx),
-                             rs * (g[i].z - sg - xh[i].z * sgx), rs * (g[i].w - sg - xh[i].w * sgx));
-      if (dres) {
-        const float4 r = ((const float4*)dres)[(long)row * d4 + c];
-        o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-      }
-      float4* p = (float4*)dx + (long)row * d4 + c;
-      if (accumulate) {
-        const float4 q = *p;
-        o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
-      }
-      *p = o;
-      if (dx16) {
-        bf16x4 ob = {f2bf(o.x), f2bf(o.y), f2bf(o.z), f2bf(o.w)};
-        ((bf16x4*)dx16)[(long)row * d4 + c] = ob;
-      }
-    }
-  }
-}
-
-// Affine LN parameter gradients: dw[c] += sum_t dy[t][c] * xhat[t][c], db[c] += sum_t dy[t][c].
-// Block = 64 columns x 256 rows (4 waves x 64 rows), LDS combine, one atomic per column per block.
-template <bool DY_F32>
-__global__ __launch_bounds__(256) void ln_dwdb_kernel(const void* __restrict__ dy_, const float* __restrict__ x,
-                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                      float* __restrict__ dw, float* __restrict__ db, int T, int d,
-                                                      RowSel sel) {
-  __shared__ float pw[4][64], pb[4][64];
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63), wv = threadIdx.x >> 6;
-  const int t0 = blockIdx.y * 256;
-  float sw = 0.f, sb = 0.f;
-  if (c < d)
-    for (int i = 0; i < 64; ++i) {
-      const int t = t0 + wv * 64 + i;
-      if (t >= T) break;
-      if (sel_hit(sel, t)) continue;
-      const float dy = DY_F32 ? ((const float*)dy_)[(long)t * d + c] : bf2f(((const __bf16*)dy_)[(long)t * d + c]);
-      sw += dy * (x[(long)t * d + c] - mean[t]) * rstd[t];
-      sb += dy;
-    }
-  pw[wv][threadIdx.x & 63] = sw;
-  pb[wv][threadIdx.x & 63] = sb;
-  __syncthreads();
-  if (wv == 0 && c < d) {
-    const int l = threadIdx.x;
-    atomicAdd(dw + c, pw[0][l] + pw[1][l] + pw[2][l] + pw[3][l]);
-    atomicAdd(db + c, pb[0][l] + pb[1][l] + pb[2][l] + pb[3][l]);
-  }
-}
-
-// Vectorised affine gradients (d % 4 == 0, 16-B aligned rows): a wave covers 256 columns as float4 lanes, the block's 4
-// waves take interleaved rows of a 32-row chunk with all 8 rows' loads issued before the first use, and the waves meet
-// in LDS for one atomic per column per block.  ~700 blocks at T = 7680 (the 64-column kernel above ran 180-360
-// blocks of 64 serial dependent loads per thread: 29 us for [7680][768], profiles/mqnli_step_breakdown_r4.txt).
-constexpr int LN_DWDB_ROWS = 32;
-template <bool DY_F32>
-__global__ __launch_bounds__(256) void ln_dwdb_vec_kernel(const void* __restrict__ dy_, const float* __restrict__ x,
-                                                          const float* __restrict__ mean,
-                                                          const float* __restrict__ rstd, float* __restrict__ dw,
-                                                          float* __restrict__ db, int T, int d, RowSel sel) {
-  __shared__ float4 pw[4][64], pb[4][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int d4 = d >> 2;
-  const int c4 = blockIdx.x * 64 + lane;
-  const int r0 = blockIdx.y * LN_DWDB_ROWS;
-  float4 sw = make_float4(0.f, 0.f, 0.f, 0.f), sb = sw;
-  if (c4 < d4) {
-    constexpr int R = LN_DWDB_ROWS / 4;
-    float4 g[R], xv[R];
-    float mu[R], rs[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      const int t = r0 + wv + 4 * i;
-      const bool live = t < T && !sel_hit(sel, t);
-      g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      xv[i] = g[i];
-      mu[i] = 0.f;
-      rs[i] = 0.f;
-      if (live) {
-        if (DY_F32) {
-          g[i] = ((const float4*)dy_)[(long)t * d4 + c4];
-        } else {
-          const bf16x4 b = ((const bf16x4*)dy_)[(long)t * d4 + c4];
-          g[i] = make_float4(bf2f(b[0]), bf2f(b[1]), bf2f(b[2]), bf2f(b[3]));
-        }
-        xv[i] = ((const float4*)x)[(long)t * d4 + c4];
-        mu[i] = mean[t];
-        rs[i] = rstd[t];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      sw.x += g[i].x * (xv[i].x - mu[i]) * rs[i];
-      sw.y += g[i].y * (xv[i].y - mu[i]) * rs[i];
-      sw.z += g[i].z * (xv[i].z - mu[i]) * rs[i];
-      sw.w += g[i].w * (xv[i].w - mu[i]) * rs[i];
-      sb.x += g[i].x; sb.y += g[i].y; sb.z += g[i].z; sb.w += g[i].w;
-    }
-  }
-  pw[wv][lane] = sw;
-  pb[wv][lane] = sb;
-  __syncthreads();
-  if (wv == 0 && c4 < d4) {
-    const float4 a = pw[0][lane], b = pw[1][lane], c = pw[2][lane], e = pw[3][lane];
-    const float4 p = pb[0][lane], q = pb[1][lane], r = pb[2][lane], u = pb[3][lane];
-    float* w4 = dw + 4 * c4;
-    float* b4 = db + 4 * c4;
-    atomicAdd(w4 + 0, (a.x + b.x) + (c.x + e.x));
-    atomicAdd(w4 + 1, (a.y + b.y) + (c.y + e.y));
-    atomicAdd(w4 + 2, (a.z + b.z) + (c.z + e.z));
-    atomicAdd(w4 + 3, (a.w + b.w) + (c.w + e.w));
-    atomicAdd(b4 + 0, (p.x + q.x) + (r.x + u.x));
-    atomicAdd(b4 + 1, (p.y + q.y) + (r.y + u.y));
-    atomicAdd(b4 + 2, (p.z + q.z) + (r.z + u.z));
-    atomicAdd(b4 + 3, (p.w + q.w) + (r.w + u.w));
-  }
-}
-
-// ln_bwd_vec_kernel with the affine gradients fused: each wave takes R rows (row = block * 4R + 4 r + wave), so a
-// lane keeps the same float4 columns for all of them and sums dy * xhat and dy in registers; the block's 4 waves
-// meet in LDS and write ONE partial row pair (dw part, db part) to ``part[block][2 d]`` with plain stores -- no
-// atomics here (the separate ln_dwdb kernels re-read dy and x and did one memory-side fp32 atomic per column per
-// 32 rows: ~17 us for [3840][768], profiles/mqnli_step_breakdown_r5.txt).  ln_part_reduce_kernel sums the partials.
-// R = rows per wave (the block covers 4 R rows): IIT_LN_PART_R = 1 / 2 / 4, default 1 -- the MQNLI (BERT-base)
-// step measured 11.93-11.96 ms at R = 1, 12.03-12.04 at 2 and 12.38-12.40 at 4 (interleaved, one box;
-// profiles/mqnli_native_r6.txt): more, shorter blocks beat the smaller partial array
-static int ln_part_r() {
-  static const int r = [] {
-    const char* e = getenv("IIT_LN_PART_R");
-    const int v = e ? atoi(e) : 1;
-    return (v == 2 || v == 4) ? v : 1;
-  }();
-  return r;
-}
-template <int V4, bool DY_F32, int LN_FUSED_R>
-__global__ __launch_bounds__(256) void ln_bwd_part_vec_kernel(const void* __restrict__ dy_, const float* __restrict__ x,
-                                                              const float* __restrict__ mean,
-                                                              const float* __restrict__ rstd,
-                                                              const float* __restrict__ w, float* __restrict__ dx,
-                                                              const float* __restrict__ dres,
-                                                              __bf16* __restrict__ dx16, float* __restrict__ part,
-                                                              int T, int d, int accumulate, RowSel sel,
-                                                              const float* __restrict__ dy2) {
-  __shared__ float4 red[2][4][64 * V4];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int d4 = d >> 2;
-  float4 pw[V4], pb[V4];
-#pragma unroll
-  for (int i = 0; i < V4; ++i) pw[i] = pb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 ww[V4];
-#pragma unroll
-  for (int i = 0; i < V4; ++i) {
-    const int c = lane + i * 64;
-    ww[i] = (w && c < d4) ? ((const float4*)w)[c] : make_float4(1.f, 1.f, 1.f, 1.f);
-  }
-  // every row's operands are loaded before the first is used: the R rows' memory latency overlaps
-  float4 dyv[LN_FUSED_R][V4], xvv[LN_FUSED_R][V4];
-  float muv[LN_FUSED_R], rsv[LN_FUSED_R];
-#pragma unroll
-  for (int r = 0; r < LN_FUSED_R; ++r) {
-    const int row = blockIdx.x * 4 * LN_FUSED_R + 4 * r + wave;
-    const bool live = row < T && !sel_hit(sel, row);
-    muv[r] = row < T ? mean[row] : 0.f;
-    rsv[r] = row < T ? rstd[row] : 0.f;
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-      const int c = lane + i * 64;
-      dyv[r][i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      xvv[r][i] = dyv[r][i];
-      if (c < d4 && live) {
-        if (DY_F32) {
-          dyv[r][i] = ((const float4*)dy_)[(long)row * d4 + c];
-        } else {
-          const bf16x4 t = ((const bf16x4*)dy_)[(long)row * d4 + c];
-          dyv[r][i] = make_float4(bf2f(t[0]), bf2f(t[1]), bf2f(t[2]), bf2f(t[3]));
-        }
-        if (dy2) {  // the fp32 twin output's gradient (LayerNormTwinFn): dy = dy + dy2
-          const float4 e = ((const float4*)dy2)[(long)row * d4 + c];
-          dyv[r][i].x += e.x; dyv[r][i].y += e.y; dyv[r][i].z += e.z; dyv[r][i].w += e.w;
-        }
-        xvv[r][i] = ((const float4*)x)[(long)row * d4 + c];
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < LN_FUSED_R; ++r) {
-    const int row = blockIdx.x * 4 * LN_FUSED_R + 4 * r + wave;
-    if (row >= T) break;
-    const bool dead = sel_hit(sel, row);
-    const float mu = muv[r], rs = rsv[r];
-    float4 g[V4], xh[V4];
-    float sg = 0.f, sgx = 0.f;
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-      float4 dy = dyv[r][i];
-      const float4 xx = xvv[r][i];
-      const float4 xv = dead ? make_float4(0.f, 0.f, 0.f, 0.f)
-                             : make_float4((xx.x - mu) * rs, (xx.y - mu) * rs, (xx.z - mu) * rs, (xx.w - mu) * rs);
-      // affine partials from the raw dy (dw += dy * xhat, db += dy), then g = dy * w
-      pw[i].x += dy.x * xv.x; pw[i].y += dy.y * xv.y; pw[i].z += dy.z * xv.z; pw[i].w += dy.w * xv.w;
-      pb[i].x += dy.x; pb[i].y += dy.y; pb[i].z += dy.z; pb[i].w += dy.w;
-      dy.x *= ww[i].x; dy.y *= ww[i].y; dy.z *= ww[i].z; dy.w *= ww[i].w;
-      g[i] = dy;
-      xh[i] = xv;
-      sg += (dy.x + dy.y) + (dy.z + dy.w);
-      sgx += (dy.x * xv.x + dy.y * xv.y) + (dy.z * xv.z + dy.w * xv.w);
-    }
-    sg = wave_sum(sg) / d;
-    sgx = wave_sum(sgx) / d;
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-      const int c = lane + i * 64;
-      if (c < d4) {
-        float4 o = make_float4(rs * (g[i].x - sg - xh[i].x * sgx), rs * (g[i].y - sg - xh[i].y * sgx),
-                               rs * (g[i].z - sg - xh[i].z * sgx), rs * (g[i].w - sg - xh[i].w * sgx));
-        if (dres) {
-          const float4 q = ((const float4*)dres)[(long)row * d4 + c];
-          o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
-        }
-        float4* p = (float4*)dx + (long)row * d4 + c;
-        if (accumulate) {
-          const float4 q = *p;
-          o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
-        }
-        *p = o;
-        if (dx16) {
-          bf16x4 ob = {f2bf(o.x), f2bf(o.y), f2bf(o.z), f2bf(o.w)};
-          ((bf16x4*)dx16)[(long)row * d4 + c] = ob;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < V4; ++i) {
-    red[0][wave][lane + i * 64] = pw[i];
-    red[1][wave][lane + i * 64] = pb[i];
-  }
-  __syncthreads();
-  // 256 threads write the block's 2 x d4 float4 partials
-  float4* out = (float4*)(part + (long)blockIdx.x * 2 * d);
-  for (int k = threadIdx.x; k < 2 * d4; k += 256) {
-    const int which = k >= d4, c = which ? k - d4 : k;
-    const float4 a = red[which][0][c], b = red[which][1][c], e = red[which][2][c], f = red[which][3][c];
-    out[k] = make_float4((a.x + b.x) + (e.x + f.x), (a.y + b.y) + (e.y + f.y), (a.z + b.z) + (e.z + f.z),
-                         (a.w + b.w) + (e.w + f.w));
-  }
-}
-
-// dw[c] += sum_b part[b][c], db[c] += sum_b part[b][d + c]: thread = one float4 column of the 2 d, blockIdx.y = one of
-// G groups of partial rows; one fp32 atomic per element per group (G <= 32)
-__global__ __launch_bounds__(256) void ln_part_reduce_kernel(const float* __restrict__ part, int nblk, int d,
-                                                             float* __restrict__ dw, float* __restrict__ db) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  const int d4 = d >> 2;
-  if (k >= 2 * d4) return;
-  const int G = gridDim.y;
-  const int per = (nblk + G - 1) / G, b0 = blockIdx.y * per, b1 = min(nblk, b0 + per);
-  if (b1 <= b0) return;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  int b = b0;
-  for (; b + 4 <= b1; b += 4) {  // four independent loads in flight
-    const float4 v0 = ((const float4*)(part + (long)b * 2 * d))[k];
-    const float4 v1 = ((const float4*)(part + (long)(b + 1) * 2 * d))[k];
-    const float4 v2 = ((const float4*)(part + (long)(b + 2) * 2 * d))[k];
-    const float4 v3 = ((const float4*)(part + (long)(b + 3) * 2 * d))[k];
-    s.x += (v0.x + v1.x) + (v2.x + v3.x);
-    s.y += (v0.y + v1.y) + (v2.y + v3.y);
-    s.z += (v0.z + v1.z) + (v2.z + v3.z);
-    s.w += (v0.w + v1.w) + (v2.w + v3.w);
-  }
-  for (; b < b1; ++b) {
-    const float4 v = ((const float4*)(part + (long)b * 2 * d))[k];
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-  }
-  float* dst = k < d4 ? dw + 4 * k : db + 4 * (k - d4);
-  atomicAdd(dst + 0, s.x);
-  atomicAdd(dst + 1, s.y);
-  atomicAdd(dst + 2, s.z);
-  atomicAdd(dst + 3, s.w);
-}
-
-// scalar fallback (any d <= 4096, any alignment)
-template <int VPL, bool DY_F32>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy_, const float* __restrict__ x,
-                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                     const float* __restrict__ w, float* __restrict__ dx,
-                                                     const float* __restrict__ dres, __bf16* __restrict__ dx16,
-                                                     int T, int d, int accumulate, RowSel sel) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= T) return;
-  const bool dead = sel_hit(sel, row);
-  const float mu = mean[row], rs = rstd[row];
-  float g[VPL], xh[VPL];
-  float sg = 0.f, sgx = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int c = lane + i * 64;
-    float dy = 0.f, xv = 0.f;
-    if (c < d && !dead) {
-      dy = DY_F32 ? ((const float*)dy_)[(long)row * d + c] : bf2f(((const __bf16*)dy_)[(long)row * d + c]);
-      xv = (x[(long)row * d + c] - mu) * rs;
-      if (w) dy *= w[c];
-    }
-    g[i] = dy;
-    xh[i] = xv;
-    sg += dy;
-    sgx += dy * xv;
-  }
-  sg = wave_sum(sg) / d;
-  sgx = wave_sum(sgx) / d;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int c = lane + i * 64;
-    if (c < d) {
-      float o = rs * (g[i] - sg - xh[i] * sgx);
-      if (dres) o += dres[(long)row * d + c];
-      float* p = dx + (long)row * d + c;
-      o = accumulate ? *p + o : o;
-      *p = o;
-      if (dx16) dx16[(long)row * d + c] = f2bf(o);
-    }
-  }
-}
-
-IIT_EXPORT int iit_ln_bwd_sel(const void* dy, int dy_f32, const float* x, const float* mean, const float* rstd,
-                              const float* w, float* dx, const float* dres, void* dx16, float* dw, float* db, int T,
-                              int d, int accumulate, unsigned long long pos_mask, int S, void* stream);
-IIT_EXPORT int iit_ln_bwd_part(const void* dy, int dy_f32, const float* x, const float* mean, const float* rstd,
-                               const float* w, float* dx, const float* dres, void* dx16, float* dw, float* db,
-                               float* part, int T, int d, int accumulate, unsigned long long pos_mask, int S,
-                               const float* dy2, void* stream);
-
-IIT_EXPORT int iit_ln_bwd(const void* dy, int dy_f32, const float* x, const float* mean, const float* rstd,
-                          const float* w, float* dx, const float* dres, void* dx16, float* dw, float* db, int T, int d,
-                          int accumulate, void* stream) {
-  return iit_ln_bwd_sel(dy, dy_f32, x, mean, rstd, w, dx, dres, dx16, dw, db, T, d, accumulate, 0ull, 1, stream);
-}
-
-// rows per block of the fused affine-gradient backward (the caller sizes ``part`` as blocks x 2 d floats)
-IIT_EXPORT int iit_ln_bwd_part_rows() { return 4 * ln_part_r(); }
-
-// iit_ln_bwd_sel with dw / db fused into the dx pass (ln_bwd_part_vec_kernel + ln_part_reduce_kernel); ``part``:
-// ceil(T / iit_ln_bwd_part_rows()) x 2 d floats of scratch; ``dy2`` (nullable, fp32 [T, d]) is added to dy.  Falls
-// back to iit_ln_bwd_sel when the vector layout does not apply (refused with a ``dy2``: the caller sums first).
-IIT_EXPORT int iit_ln_bwd_part(const void* dy, int dy_f32, const float* x, const float* mean, const float* rstd,
-                               const float* w, float* dx, const float* dres, void* dx16, float* dw, float* db,
-                               float* part, int T, int d, int accumulate, unsigned long long pos_mask, int S,
-                               const float* dy2, void* stream) {
-  const bool vec = part && dw && db && d % 4 == 0 && d <= 1024 && aligned16(x) && aligned16(dx) &&
-                   (!dres || aligned16(dres)) && (!w || aligned16(w)) && aligned16(dw) && aligned16(db) &&
-                   aligned16(part) && (dy_f32 ? aligned16(dy) : (((uintptr_t)dy) & 7) == 0) &&
-                   (((uintptr_t)dx16) & 7) == 0 && (!dy2 || aligned16(dy2));
-  if (dy2 && !vec) return (int)hipErrorInvalidValue;
-  if (!vec || T <= 0)
-    return iit_ln_bwd_sel(dy, dy_f32, x, mean, rstd, w, dx, dres, dx16, dw, db, T, d, accumulate, pos_mask, S, stream);
-  if (pos_mask && (S <= 0 || S > 64)) return (int)hipErrorInvalidValue;
-  const RowSel sel{pos_mask, S > 0 ? S : 1, T};
-  const int R = ln_part_r();
-  const int nblk = (T + 4 * R - 1) / (4 * R);
-  hipStream_t s = (hipStream_t)stream;
-  __bf16* d16 = (__bf16*)dx16;
-#define LNPR(V, RR)                                                                                              \
-  if (dy_f32) hipLaunchKernelGGL((ln_bwd_part_vec_kernel<V, true, RR>), dim3(nblk), dim3(256), 0, s, dy, x, mean, rstd, w, dx, dres, d16, part, T, d, accumulate, sel, dy2); \
-  else hipLaunchKernelGGL((ln_bwd_part_vec_kernel<V, false, RR>), dim3(nblk), dim3(256), 0, s, dy, x, mean, rstd, w, dx, dres, d16, part, T, d, accumulate, sel, dy2);
-#define LNP(V) if (R == 1) { LNPR(V, 1) } else if (R == 4) { LNPR(V, 4) } else { LNPR(V, 2) }
-  const int v4 = (d / 4 + 63) / 64;
-  if (v4 <= 1) { LNP(1) } else if (v4 <= 2) { LNP(2) } else if (v4 <= 3) { LNP(3) } else { LNP(4) }
-#undef LNP
-#undef LNPR
-  static const int gcap = [] {  // IIT_LN_REDUCE_G: most groups of partial rows (default 32)
-    const char* e = getenv("IIT_LN_REDUCE_G");
-    const int v = e ? atoi(e) : 32;
-    return v >= 1 && v <= 1024 ? v : 32;
-  }();
-  const int G = max(1, min(gcap, nblk / 8));  // >= ~8 partial rows per thread
-  hipLaunchKernelGGL(ln_part_reduce_kernel, dim3((2 * (d / 4) + 255) / 256, G), dim3(256), 0, s, part, nblk, d, dw, db);
-  return hipGetLastError();
-}
-
-// LNPre backward from the forward's bf16 output (``xh`` = xhat, [T, d]); no affine parameters, no row select
-IIT_EXPORT int iit_ln_bwd_xh16(const void* dy, int dy_f32, const void* xh, const float* rstd, float* dx,
-                               const float* dres, void* dx16, int T, int d, int accumulate, void* stream) {
-  if (d % 4 || d > 4096 || (((uintptr_t)xh) & 7) || !aligned16(dx) || (dres && !aligned16(dres)) ||
-      (dy_f32 ? !aligned16(dy) : (((uintptr_t)dy) & 7) != 0) || (((uintptr_t)dx16) & 7))
-    return (int)hipErrorInvalidValue;
-  const RowSel sel{0ull, 1, T};
-  dim3 grid((T + 3) / 4), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  __bf16* d16 = (__bf16*)dx16;
-  const float* x = (const float*)xh;
-#define LNBX(V)                                                                                                   \
-  if (dy_f32) hipLaunchKernelGGL((ln_bwd_vec_kernel<V, true, true>), grid, block, 0, s, dy, x, rstd, rstd, nullptr, dx, dres, d16, T, d, accumulate, sel); \
-  else hipLaunchKernelGGL((ln_bwd_vec_kernel<V, false, true>), grid, block, 0, s, dy, x, rstd, rstd, nullptr, dx, dres, d16, T, d, accumulate, sel);
-  const int v4 = (d / 4 + 63) / 64;
-  if (v4 <= 1) { LNBX(1) } else if (v4 <= 2) { LNBX(2) } else if (v4 <= 3) { LNBX(3) } else if (v4 <= 4) { LNBX(4) }
-  else if (v4 <= 6) { LNBX(6) } else if (v4 <= 8) { LNBX(8) } else if (v4 <= 12) { LNBX(12) } else { LNBX(16) }
-#undef LNBX
-  return hipGetLastError();
-}
-
-// backward of iit_ln_fwd_sel over the base rows (T = Tb): rows at masked positions get dx = dres only and add
-// nothing to dw / db
-IIT_EXPORT int iit_ln_bwd_sel(const void* dy, int dy_f32, const float* x, const float* mean, const float* rstd,
-                              const float* w, float* dx, const float* dres, void* dx16, float* dw, float* db, int T,
-                              int d, int accumulate, unsigned long long pos_mask, int S, void* stream) {
-  const RowSel sel{pos_mask, S > 0 ? S : 1, T};
-  if (pos_mask && (S <= 0 || S > 64)) return (int)hipErrorInvalidValue;
-  dim3 grid((T + 3) / 4), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  __bf16* d16 = (__bf16*)dx16;
-  const bool vec = d % 4 == 0 && d <= 4096 && aligned16(x) && aligned16(dx) && (!dres || aligned16(dres)) &&
-                   (!w || aligned16(w)) && (dy_f32 ? aligned16(dy) : (((uintptr_t)dy) & 7) == 0) &&
-                   (((uintptr_t)dx16) & 7) == 0;
-  if (vec) {
-#define LNBV(V)                                                                                                   \
-  if (dy_f32) hipLaunchKernelGGL((ln_bwd_vec_kernel<V, true>), grid, block, 0, s, dy, x, mean, rstd, w, dx, dres, d16, T, d, accumulate, sel); \
-  else hipLaunchKernelGGL((ln_bwd_vec_kernel<V, false>), grid, block, 0, s, dy, x, mean, rstd, w, dx, dres, d16, T, d, accumulate, sel);
-    const int v4 = (d / 4 + 63) / 64;
-    if (v4 <= 1) { LNBV(1) } else if (v4 <= 2) { LNBV(2) } else if (v4 <= 3) { LNBV(3) } else if (v4 <= 4) { LNBV(4) }
-    else if (v4 <= 6) { LNBV(6) } else if (v4 <= 8) { LNBV(8) } else if (v4 <= 12) { LNBV(12) } else { LNBV(16) }
-#undef LNBV
-  } else {
-#define LNB(V)                                                                                                   \
-  if (dy_f32) hipLaunchKernelGGL((ln_bwd_kernel<V, true>), grid, block, 0, s, dy, x, mean, rstd, w, dx, dres, d16, T, d, accumulate, sel); \
-  else hipLaunchKernelGGL((ln_bwd_kernel<V, false>), grid, block, 0, s, dy, x, mean, rstd, w, dx, dres, d16, T, d, accumulate, sel);
-    if (d <= 256) { LNB(4) }
-    else if (d <= 1024) { LNB(16) }
-    else if (d <= 2048) { LNB(32) }
-    else if (d <= 4096) { LNB(64) }
-    else return (int)hipErrorInvalidValue;
-#undef LNB
-  }
-  if (dw) {
-    const bool v4 = d % 4 == 0 && aligned16(x) && aligned16(dw) && aligned16(db) &&
-                    (dy_f32 ? aligned16(dy) : (((uintptr_t)dy) & 7) == 0);
-    if (v4) {
-      dim3 g2((d / 4 + 63) / 64, (T + LN_DWDB_ROWS - 1) / LN_DWDB_ROWS);
-      if (dy_f32) hipLaunchKernelGGL(ln_dwdb_vec_kernel<true>, g2, block, 0, s, dy, x, mean, rstd, dw, db, T, d, sel);
-      else hipLaunchKernelGGL(ln_dwdb_vec_kernel<false>, g2, block, 0, s, dy, x, mean, rstd, dw, db, T, d, sel);
-    } else {
-      dim3 g2((d + 63) / 64, (T + 255) / 256);
-      if (dy_f32) hipLaunchKernelGGL(ln_dwdb_kernel<true>, g2, block, 0, s, dy, x, mean, rstd, dw, db, T, d, sel);
-      else hipLaunchKernelGGL(ln_dwdb_kernel<false>, g2, block, 0, s, dy, x, mean, rstd, dw, db, T, d, sel);
-    }
   }
   return hipGetLastError();
 }

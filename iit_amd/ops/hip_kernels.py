@@ -39,13 +39,8 @@ _SIGS = {
     "iit_gemm_glds_sm": [c_void_p] * 8 + [c_long] * 5 + [c_int] * 8 + [c_void_p] * 3 + [c_int] + [c_void_p] * 3,
     "iit_embed_pos_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "iit_embed_pos_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "iit_ln_fwd": [c_void_p] * 6 + [c_int, c_int, c_float, c_void_p],
-    "iit_ln_bwd": [c_void_p, c_int] + [c_void_p] * 9 + [c_int, c_int, c_int, c_void_p],
-    "iit_ln_fwd_sel": [c_void_p] * 6 + [c_int, c_int, c_float, c_ull, c_int, c_int, c_void_p],
-    "iit_ln_bwd_xh16": [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p],
-    "iit_ln_bwd_sel": [c_void_p, c_int] + [c_void_p] * 9 + [c_int, c_int, c_int, c_ull, c_int, c_void_p],
-    "iit_ln_bwd_part": [c_void_p, c_int] + [c_void_p] * 10 + [c_int, c_int, c_int, c_ull, c_int, c_void_p, c_void_p],
-    "iit_ln_fwd_twin": [c_void_p] * 7 + [c_int, c_int, c_float, c_void_p],
+    "iit_ln_fwd": [c_void_p] * 7 + [c_int, c_int, c_float, c_ull, c_int, c_int, c_void_p],
+    "iit_ln_bwd": [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 10 + [c_int, c_int, c_int, c_ull, c_int, c_void_p],
     "iit_ln_bwd_part_rows": [],
     "iit_attn_small_fwd": [c_void_p] * 4 + [c_ull, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_float, c_int,
                                             c_void_p],
@@ -566,23 +561,35 @@ def embed_pos_bwd(tokens, g, dWE, dWpos, B, S, d):
     _check(lib().iit_embed_pos_bwd(_p(tokens), _p(g), _p(dWE), _p(dWpos), B, S, d, _stream()), "embed_pos_bwd")
 
 
-def ln_fwd(x, w, b, y, mean, rstd, T, d, eps):
+def _ln_fwd(what, x, w, b, y, y32, mean, rstd, T, d, eps, pos_mask=0, S=1, Tb=0) -> int:
     if CHECK_BOUNDS:
-        _bounds("ln_fwd", ("x", x, T, d, d), ("y", y, T, d, d), ("mean", mean, 1, T, T), ("rstd", rstd, 1, T, T))
-    _check(lib().iit_ln_fwd(_p(x), _p(w), _p(b), _p(y), _p(mean), _p(rstd), T, d, eps, _stream()), "ln_fwd")
+        _bounds(what, ("x", x, T, d, d), ("y", y, T, d, d), ("y32", y32, T, d, d), ("mean", mean, 1, T, T),
+                ("rstd", rstd, 1, T, T))
+    return lib().iit_ln_fwd(_p(x), _p(w), _p(b), _p(y), _p(y32), _p(mean), _p(rstd), T, d, eps, pos_mask, S, Tb, _stream())
+
+
+def ln_fwd(x, w, b, y, mean, rstd, T, d, eps):
+    _check(_ln_fwd("ln_fwd", x, w, b, y, None, mean, rstd, T, d, eps), "ln_fwd")
 
 
 def ln_fwd_twin(x, w, b, y, y32, mean, rstd, T, d, eps) -> bool:
     """``ln_fwd`` that also writes ``y32`` = fp32(y) in the same pass; False when the vector layout does not apply
     (nothing launched: the caller casts)."""
-    if CHECK_BOUNDS:
-        _bounds("ln_fwd_twin", ("x", x, T, d, d), ("y", y, T, d, d), ("y32", y32, T, d, d))
-    return lib().iit_ln_fwd_twin(_p(x), _p(w), _p(b), _p(y), _p(y32), _p(mean), _p(rstd), T, d, eps, _stream()) == 0
+    return _ln_fwd("ln_fwd_twin", x, w, b, y, y32, mean, rstd, T, d, eps) == 0
+
+
+def ln_fwd_sel(x, w, b, y, mean, rstd, T, d, eps, pos_mask: int, S: int, Tb: int):
+    """``ln_fwd`` over paired rows with the whole-position splice inside the kernel: base rows [0, Tb) at positions
+    whose bit is set in ``pos_mask`` normalise the source row ``row + Tb`` (csrc/layer_norm.hip RowSel)."""
+    _check(_ln_fwd("ln_fwd_sel", x, w, b, y, None, mean, rstd, T, d, eps, pos_mask, S, Tb), "ln_fwd_sel")
+
+
+_LN_PART_ROWS = [0]
 
 
 def _ln_part(dw, T: int, d: int):
-    """Scratch of the fused affine-gradient LN backward (``iit_ln_bwd_part``): one (dw, db) partial row pair per
-    block of ``iit_ln_bwd_part_rows()`` rows; None without affine gradients or with ``IIT_LN_FUSED_DWDB=0``."""
+    """Scratch of the fused affine-gradient LN backward: one (dw, db) partial row pair per block of
+    ``iit_ln_bwd_part_rows()`` rows; None without affine gradients or with ``IIT_LN_FUSED_DWDB=0``."""
     if dw is None or os.environ.get("IIT_LN_FUSED_DWDB", "1") == "0":
         return None
     rows = _LN_PART_ROWS[0] or lib().iit_ln_bwd_part_rows()
@@ -590,61 +597,41 @@ def _ln_part(dw, T: int, d: int):
     return torch.empty(((T + rows - 1) // rows) * 2 * d, dtype=torch.float32, device=dw.device)
 
 
-_LN_PART_ROWS = [0]
+def _ln_bwd(what, dy, x, mean, rstd, w, dx, dw, db, T, d, *, accumulate=False, dres=None, dx16=None, dy2=None,
+            pos_mask=0, S=1, xh16=False):
+    """``iit_ln_bwd`` with the fused affine gradients where they apply (``_ln_part``), else the dx kernel and a dwdb
+    kernel; a ``dy2`` the kernel refuses (no fused path) is summed into ``dy`` here."""
+    if CHECK_BOUNDS:
+        _bounds(what, ("dy", dy, T, d, d), ("x", x, T, d, d), ("dx", dx, T, d, d), ("dres", dres, T, d, d),
+                ("dx16", dx16, T, d, d), ("mean", mean, 1, T, T), ("rstd", rstd, 1, T, T), ("dy2", dy2, T, d, d))
+
+    def launch(dy, part, dy2):
+        return lib().iit_ln_bwd(_p(dy), int(dy.dtype == torch.float32), _p(x), int(xh16),
+                                _p(mean), _p(rstd), _p(w), _p(dx), _p(dres), _p(dx16), _p(dw), _p(db), _p(part),
+                                _p(dy2), T, d, int(accumulate), pos_mask, S, _stream())
+
+    rc = launch(dy, _ln_part(dw, T, d), dy2)
+    if rc != 0 and dy2 is not None:  # (no fused path: sum the two gradients first)
+        rc = launch(dy.float() + dy2, None, None)
+    _check(rc, what)
 
 
 def ln_bwd(dy, x, mean, rstd, w, dx, dw, db, T, d, accumulate=False, dres=None, dx16=None, dy2=None):
     """dx = LN'(dy) (+ dres, the skip-connection gradient, fp32 [T, d]); ``dx16`` (optional) gets a bf16 copy; with
-    ``dw`` / ``db`` the affine gradients are added in the same pass (``iit_ln_bwd_part``); ``dy2`` (fp32 [T, d],
-    optional) is a second gradient of the output, added to ``dy`` inside the kernel where it can be."""
-    if CHECK_BOUNDS:
-        _bounds("ln_bwd", ("dy", dy, T, d, d), ("x", x, T, d, d), ("dx", dx, T, d, d), ("dres", dres, T, d, d),
-                ("dx16", dx16, T, d, d), ("mean", mean, 1, T, T), ("dy2", dy2, T, d, d))
-    part = _ln_part(dw, T, d)
-    if part is not None:
-        rc = lib().iit_ln_bwd_part(_p(dy), int(dy.dtype == torch.float32), _p(x), _p(mean), _p(rstd), _p(w),
-                                   _p(dx), _p(dres), _p(dx16), _p(dw), _p(db), _p(part), T, d, int(accumulate), 0,
-                                   1, _p(dy2), _stream())
-        if rc == 0 or dy2 is None:
-            _check(rc, "ln_bwd_part")
-            return
-    if dy2 is not None:  # (no fused path: sum the two gradients first)
-        dy = dy.float() + dy2
-    _check(lib().iit_ln_bwd(_p(dy), int(dy.dtype == torch.float32), _p(x), _p(mean), _p(rstd), _p(w), _p(dx),
-                            _p(dres), _p(dx16), _p(dw), _p(db), T, d, int(accumulate), _stream()), "ln_bwd")
+    ``dw`` / ``db`` the affine gradients are added in the same pass; ``dy2`` (fp32 [T, d], optional) is a second
+    gradient of the output, added to ``dy`` inside the kernel where it can be."""
+    _ln_bwd("ln_bwd", dy, x, mean, rstd, w, dx, dw, db, T, d, accumulate=accumulate, dres=dres, dx16=dx16, dy2=dy2)
 
 
 def ln_bwd_xh16(dy, xh, rstd, dx, T, d, dres=None, dx16=None):
     """LNPre backward from the forward's bf16 output ``xh`` (= xhat; 2 B per element instead of the fp32 input)."""
-    if CHECK_BOUNDS:
-        _bounds("ln_bwd_xh16", ("dy", dy, T, d, d), ("xh", xh, T, d, d), ("dx", dx, T, d, d), ("dres", dres, T, d, d),
-                ("dx16", dx16, T, d, d), ("rstd", rstd, 1, T, T))
     assert xh.dtype == torch.bfloat16
-    _check(lib().iit_ln_bwd_xh16(_p(dy), int(dy.dtype == torch.float32), _p(xh), _p(rstd), _p(dx), _p(dres),
-                                 _p(dx16), T, d, 0, _stream()), "ln_bwd_xh16")
-
-
-def ln_fwd_sel(x, w, b, y, mean, rstd, T, d, eps, pos_mask: int, S: int, Tb: int):
-    """``ln_fwd`` over paired rows with the whole-position splice inside the kernel: base rows [0, Tb) at positions
-    whose bit is set in ``pos_mask`` normalise the source row ``row + Tb`` (csrc/kernels.hip RowSel)."""
-    if CHECK_BOUNDS:
-        _bounds("ln_fwd_sel", ("x", x, T, d, d), ("y", y, T, d, d), ("mean", mean, 1, T, T), ("rstd", rstd, 1, T, T))
-    _check(lib().iit_ln_fwd_sel(_p(x), _p(w), _p(b), _p(y), _p(mean), _p(rstd), T, d, eps, pos_mask, S, Tb, _stream()), "ln_fwd_sel")
+    _ln_bwd("ln_bwd_xh16", dy, xh, None, rstd, None, dx, None, None, T, d, dres=dres, dx16=dx16, xh16=True)
 
 
 def ln_bwd_sel(dy, x, mean, rstd, w, dx, dw, db, T, d, pos_mask: int, S: int, dres=None, dx16=None):
     """Backward of :func:`ln_fwd_sel` over the base rows: spliced rows pass only ``dres`` and add nothing to dw/db."""
-    if CHECK_BOUNDS:
-        _bounds("ln_bwd_sel", ("dy", dy, T, d, d), ("x", x, T, d, d), ("dx", dx, T, d, d), ("mean", mean, 1, T, T))
-    part = _ln_part(dw, T, d)
-    if part is not None:
-        _check(lib().iit_ln_bwd_part(_p(dy), int(dy.dtype == torch.float32), _p(x), _p(mean), _p(rstd), _p(w),
-                                     _p(dx), _p(dres), _p(dx16), _p(dw), _p(db), _p(part), T, d, 0, pos_mask, S,
-                                     None, _stream()), "ln_bwd_sel_part")
-        return
-    _check(lib().iit_ln_bwd_sel(_p(dy), int(dy.dtype == torch.float32), _p(x), _p(mean), _p(rstd), _p(w), _p(dx),
-                                _p(dres), _p(dx16), _p(dw), _p(db), T, d, 0, pos_mask, S,
-                                _stream()), "ln_bwd_sel")
+    _ln_bwd("ln_bwd_sel", dy, x, mean, rstd, w, dx, dw, db, T, d, dres=dres, dx16=dx16, pos_mask=pos_mask, S=S)
 
 
 def heads_to_mask(heads: Optional[Sequence[int]]) -> int:

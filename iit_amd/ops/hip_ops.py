@@ -428,45 +428,96 @@ class EmbedPosFn(Function):
         return None, None, None
 
 
+def _xhat16(w, b, d: int) -> bool:
+    """The LN backward reads the forward's bf16 output as xhat (norms without weight and bias: 2 B per element instead
+    of the fp32 input).  Round 3 reverted it over a staged-backward mismatch that round 4 traced to the split-store GEMM
+    candidate (profiles/split_store_removal_r4.txt); ``IIT_LN_XHAT16=0`` reads the fp32 input."""
+    return w is None and b is None and d % 4 == 0 and d <= 4096 and os.environ.get("IIT_LN_XHAT16", "1") == "1"
+
+
+def _ln_forward(ctx, x, w, b, eps, x_full=None, twin=False, xhat16=False, pos_mask=0):
+    """Forward of every LN Function: one launch over the rows of ``x`` -- of ``x_full`` (base rows first, then the
+    source rows) for the paired classes -- that saves the base rows for the backward: their fp32 input, or with
+    ``xhat16`` their bf16 output.  Returns ``(y, y32)`` in the shape of the rows' tensor; ``y32`` (``twin``) is the fp32
+    image of ``y`` from the same pass, None otherwise.  Both are allocated in that shape (outputs that are views
+    could not be modified in place downstream of a multi-output Function), except with ``xhat16`` (the Fork classes)."""
+    ctx.set_materialize_grads(False)
+    rows = x if x_full is None else x_full
+    lead, d = rows.shape[:-1], rows.shape[-1]
+    x2 = _flat2(rows.float().contiguous())
+    T2 = x2.shape[0]
+    T = T2 * x.shape[0] // rows.shape[0]  # base rows
+    S = x.shape[1] if x.dim() == 3 else 1
+    if xhat16:
+        # the saved xhat is the 2-D buffer and the output a view of it: saving a view OF the output would close the
+        # cycle output -> grad_fn -> saved view -> its base, and a forward that is never backwarded would not be freed
+        yf = torch.empty(T2, d, dtype=BF16, device=x.device)
+        y = yf.view(*lead, d)
+    else:
+        y = torch.empty(*lead, d, dtype=BF16, device=x.device)
+        yf = y.view(T2, d)
+    y32 = torch.empty(*lead, d, dtype=F32, device=x.device) if twin else None
+    mean = torch.empty(T2, dtype=F32, device=x.device)
+    rstd = torch.empty(T2, dtype=F32, device=x.device)
+    if pos_mask:  # whole-position splice of the base rows from the source rows, inside the LN kernel
+        K.ln_fwd_sel(x2, w, b, yf, mean, rstd, T2, d, eps, pos_mask, S, T)
+    elif not twin or not K.ln_fwd_twin(x2, w, b, yf, y32.view(T2, d), mean, rstd, T2, d, eps):
+        K.ln_fwd(x2, w, b, yf, mean, rstd, T2, d, eps)
+        if twin:
+            y32.copy_(y)
+    ctx.save_for_backward((yf if xhat16 else x2)[:T], mean[:T], rstd[:T])
+    ctx.params = (w, b)
+    ctx.in_dtype = x.dtype
+    ctx.sel = (pos_mask, S)
+    return y, y32
+
+
+def _ln_backward(ctx, dy, dres=None, dy2=None, sel=None):
+    """The gradient of ``x`` for every LN Function.  ``dres``: the gradient of a residual passthrough output, added
+    inside the kernel (returned as it is when ``dy`` is missing); ``dy2``: the gradient of the fp32 twin output, added
+    to ``dy`` inside the kernel (it stands in for a missing ``dy``); ``sel`` = (pos_mask, S) of a row-select forward.
+    An fp32 ``x`` gets its gradient with the bf16 copy attached, any other dtype a cast of it."""
+    if dy is None and dy2 is not None:
+        dy, dy2 = dy2.float(), None
+    if dy is None:
+        return dres
+    xs, mean, rstd = ctx.saved_tensors
+    w, b = ctx.params
+    T, d = xs.shape
+    g = _flat2(dy.contiguous())
+    g2 = None if dy2 is None else _flat2(dy2.float().contiguous())
+    dres = None if dres is None else _flat2(dres.float().contiguous())
+    dx = torch.empty(T, d, dtype=F32, device=xs.device)
+    dx16 = torch.empty(T, d, dtype=BF16, device=xs.device) if ctx.in_dtype == F32 else None
+    if xs.dtype == BF16:  # the saved rows are xhat (_xhat16: no affine parameters)
+        K.ln_bwd_xh16(g, xs, rstd, dx, T, d, dres=dres, dx16=dx16)
+    else:
+        dw = _grad_slot(w) if w is not None else None
+        db = _grad_slot(b) if b is not None else None
+        if sel is not None and sel[0]:
+            K.ln_bwd_sel(g, xs, mean, rstd, w, dx, dw, db, T, d, sel[0], sel[1], dres=dres, dx16=dx16)
+        else:
+            K.ln_bwd(g, xs, mean, rstd, w, dx, dw, db, T, d, dres=dres, dx16=dx16, dy2=g2)
+        _done(w, b)
+    dx = dx.view(*dy.shape[:-1], d)
+    if dx16 is None:
+        return dx.to(ctx.in_dtype)
+    _set_bf16_twin(dx, dx16)
+    return dx
+
+
 class LayerNormFn(Function):
     @staticmethod
     def forward(ctx, x, w, b, eps):
-        ctx.set_materialize_grads(False)
-        shape = x.shape
-        d = shape[-1]
-        x2 = _flat2(x.float().contiguous())
-        T = x2.shape[0]
-        y = torch.empty(T, d, dtype=BF16, device=x.device)
-        mean = torch.empty(T, dtype=F32, device=x.device)
-        rstd = torch.empty(T, dtype=F32, device=x.device)
-        K.ln_fwd(x2, w, b, y, mean, rstd, T, d, eps)
-        ctx.save_for_backward(x2, mean, rstd)
-        ctx.params = (w, b)
-        ctx.in_dtype = x.dtype
-        return y.view(*shape[:-1], d)
+        return _ln_forward(ctx, x, w, b, eps)[0]
 
     @staticmethod
     def backward(ctx, dy):
-        if dy is None:
-            return None, None, None, None
-        x2, mean, rstd = ctx.saved_tensors
-        w, b = ctx.params
-        T, d = x2.shape
-        dx = torch.empty(T, d, dtype=F32, device=x2.device)
-        dx16 = torch.empty(T, d, dtype=BF16, device=x2.device) if ctx.in_dtype == F32 else None
-        dw = _grad_slot(w) if w is not None else None
-        db = _grad_slot(b) if b is not None else None
-        K.ln_bwd(_flat2(dy.contiguous()), x2, mean, rstd, w, dx, dw, db, T, d, dx16=dx16)
-        _done(w, b)
-        dx = dx.view(*dy.shape[:-1], d)
-        if dx16 is None:
-            return dx.to(ctx.in_dtype), None, None, None
-        _set_bf16_twin(dx, dx16)
-        return dx, None, None, None
+        return _ln_backward(ctx, dy), None, None, None
 
 
 class LayerNormTwinFn(Function):
-    """``(LN(x), fp32(LN(x)))`` from one kernel pass (``iit_ln_fwd_twin``): a post-norm block (BERT) feeds the bf16
+    """``(LN(x), fp32(LN(x)))`` from one kernel pass (``ln_fwd_twin``): a post-norm block (BERT) feeds the bf16
     output to the next GEMM and the fp32 copy to the residual epilogue of the GEMM after it, which read a cast of
     the bf16 output before -- a [T, d] cast pass forward, and backward a cast of the residual gradient plus
     autograd's bf16 sum of the two gradients.  The backward takes both gradients and adds the fp32 one inside the
@@ -474,50 +525,11 @@ class LayerNormTwinFn(Function):
 
     @staticmethod
     def forward(ctx, x, w, b, eps):
-        ctx.set_materialize_grads(False)
-        shape = x.shape
-        d = shape[-1]
-        x2 = _flat2(x.float().contiguous())
-        T = x2.shape[0]
-        # allocated in the output shape (the outputs are not views: a multi-output Function's views may not be
-        # modified in place downstream)
-        y = torch.empty(*shape[:-1], d, dtype=BF16, device=x.device)
-        y32 = torch.empty(*shape[:-1], d, dtype=F32, device=x.device)
-        mean = torch.empty(T, dtype=F32, device=x.device)
-        rstd = torch.empty(T, dtype=F32, device=x.device)
-        yf, y32f = y.view(T, d), y32.view(T, d)
-        if not K.ln_fwd_twin(x2, w, b, yf, y32f, mean, rstd, T, d, eps):
-            K.ln_fwd(x2, w, b, yf, mean, rstd, T, d, eps)
-            y32f.copy_(yf)
-        ctx.save_for_backward(x2, mean, rstd)
-        ctx.params = (w, b)
-        ctx.in_dtype = x.dtype
-        return y, y32
+        return _ln_forward(ctx, x, w, b, eps, twin=True)
 
     @staticmethod
     def backward(ctx, dy, dy32):
-        if dy is None and dy32 is None:
-            return None, None, None, None
-        x2, mean, rstd = ctx.saved_tensors
-        w, b = ctx.params
-        T, d = x2.shape
-        lead = (dy if dy is not None else dy32).shape[:-1]
-        dx = torch.empty(T, d, dtype=F32, device=x2.device)
-        dx16 = torch.empty(T, d, dtype=BF16, device=x2.device) if ctx.in_dtype == F32 else None
-        dw = _grad_slot(w) if w is not None else None
-        db = _grad_slot(b) if b is not None else None
-        if dy is None:
-            g, g2 = _flat2(dy32.float().contiguous()), None
-        else:
-            g = _flat2(dy.contiguous())
-            g2 = None if dy32 is None else _flat2(dy32.float().contiguous())
-        K.ln_bwd(g, x2, mean, rstd, w, dx, dw, db, T, d, dx16=dx16, dy2=g2)
-        _done(w, b)
-        dx = dx.view(*lead, d)
-        if dx16 is None:
-            return dx.to(ctx.in_dtype), None, None, None
-        _set_bf16_twin(dx, dx16)
-        return dx, None, None, None
+        return _ln_backward(ctx, dy, dy2=dy32), None, None, None
 
 
 def _f32_of(t: torch.Tensor) -> torch.Tensor:
@@ -546,61 +558,18 @@ def _bf16_of(t: torch.Tensor) -> torch.Tensor:
     return t.to(BF16)
 
 
-def _xhat16(w, b, d: int) -> bool:
-    """The LN backward reads the forward's bf16 output as xhat (norms without weight and bias: 2 B per element instead
-    of the fp32 input).  Round 3 reverted it over a staged-backward mismatch that round 4 traced to the split-store GEMM
-    candidate (profiles/split_store_removal_r4.txt); ``IIT_LN_XHAT16=0`` reads the fp32 input."""
-    return w is None and b is None and d % 4 == 0 and d <= 4096 and os.environ.get("IIT_LN_XHAT16", "1") == "1"
-
-
-def _ln_fork_bwd(ctx, dy, dpass):
-    xs, mean, rstd = ctx.saved_tensors
-    w, b = ctx.params
-    T, d = xs.shape
-    dres = None
-    if dpass is not None:
-        dres = _flat2(dpass.float().contiguous())
-    dx = torch.empty(T, d, dtype=F32, device=xs.device)
-    dx16 = torch.empty(T, d, dtype=BF16, device=xs.device) if ctx.in_dtype == F32 else None
-    if xs.dtype == BF16:
-        K.ln_bwd_xh16(_flat2(dy.contiguous()), xs, rstd, dx, T, d, dres=dres, dx16=dx16)
-    else:
-        dw = _grad_slot(w) if w is not None else None
-        db = _grad_slot(b) if b is not None else None
-        K.ln_bwd(_flat2(dy.contiguous()), xs, mean, rstd, w, dx, dw, db, T, d, dres=dres, dx16=dx16)
-        _done(w, b)
-    dx = dx.view(*dy.shape[:-1], d)
-    if dx16 is None:
-        return dx.to(ctx.in_dtype), None, None, None
-    _set_bf16_twin(dx, dx16)
-    return dx, None, None, None
-
-
 class LayerNormForkFn(Function):
     """``(LN(x), x)``: the second output carries the residual stream past the norm, so the backward gets
     both gradients and sums them inside the LN-backward kernel (no separate autograd add over [T, d])."""
 
     @staticmethod
     def forward(ctx, x, w, b, eps):
-        ctx.set_materialize_grads(False)
-        shape = x.shape
-        d = shape[-1]
-        x2 = _flat2(x.float().contiguous())
-        T = x2.shape[0]
-        y = torch.empty(T, d, dtype=BF16, device=x.device)
-        mean = torch.empty(T, dtype=F32, device=x.device)
-        rstd = torch.empty(T, dtype=F32, device=x.device)
-        K.ln_fwd(x2, w, b, y, mean, rstd, T, d, eps)
-        ctx.save_for_backward(y if _xhat16(w, b, d) else x2, mean, rstd)
-        ctx.params = (w, b)
-        ctx.in_dtype = x.dtype
-        return y.view(*shape[:-1], d), x.view_as(x)
+        y, _ = _ln_forward(ctx, x, w, b, eps, xhat16=_xhat16(w, b, x.shape[-1]))
+        return y, x.view_as(x)
 
     @staticmethod
     def backward(ctx, dy, dpass):
-        if dy is None:
-            return dpass, None, None, None
-        return _ln_fork_bwd(ctx, dy, dpass)
+        return _ln_backward(ctx, dy, dres=dpass), None, None, None
 
 
 def _packed3(a: Optional[torch.Tensor], b: Optional[torch.Tensor], c: Optional[torch.Tensor], n: int) -> bool:
@@ -1405,22 +1374,9 @@ class EmbedPosPairFn(EmbedPosFn):
 class LayerNormForkPairFn(LayerNormForkFn):
     @staticmethod
     def forward(ctx, x, w, b, eps, x_full, box):
-        ctx.set_materialize_grads(False)
-        d = x.shape[-1]
-        B = x.shape[0]
-        x2 = _flat2(x_full)
-        T2 = x2.shape[0]
-        T = T2 * B // x_full.shape[0]
-        y = torch.empty(T2, d, dtype=BF16, device=x.device)
-        mean = torch.empty(T2, dtype=F32, device=x.device)
-        rstd = torch.empty(T2, dtype=F32, device=x.device)
-        K.ln_fwd(x2, w, b, y, mean, rstd, T2, d, eps)
-        ctx.save_for_backward(y[:T] if _xhat16(w, b, d) else x2[:T], mean[:T], rstd[:T])
-        ctx.params = (w, b)
-        ctx.in_dtype = x.dtype
-        yf = y.view(*x_full.shape[:-1], d)
+        yf, _ = _ln_forward(ctx, x, w, b, eps, x_full, xhat16=_xhat16(w, b, x.shape[-1]))
         box.append(yf)
-        return yf[:B], x.view_as(x)
+        return yf[:x.shape[0]], x.view_as(x)
 
     @staticmethod
     def backward(ctx, dy, dpass):
@@ -1429,31 +1385,14 @@ class LayerNormForkPairFn(LayerNormForkFn):
 
 class LayerNormPairTwinFn(Function):
     """:class:`LayerNormPairFn` (no position splice) that also writes the fp32 twin of both row sets in the same
-    pass (``iit_ln_fwd_twin``) -- :class:`LayerNormTwinFn` for the paired forward: outputs (base bf16, base fp32),
+    pass (``ln_fwd_twin``) -- :class:`LayerNormTwinFn` for the paired forward: outputs (base bf16, base fp32),
     ``box`` gets (full bf16, full fp32); the backward adds the fp32 output's gradient inside the LN backward."""
 
     @staticmethod
     def forward(ctx, x, w, b, eps, x_full, box):
-        ctx.set_materialize_grads(False)
-        d = x.shape[-1]
-        B = x.shape[0]
-        x2 = _flat2(x_full)
-        T2 = x2.shape[0]
-        T = T2 * B // x_full.shape[0]
-        y = torch.empty(T2, d, dtype=BF16, device=x.device)
-        y32 = torch.empty(T2, d, dtype=F32, device=x.device)
-        mean = torch.empty(T2, dtype=F32, device=x.device)
-        rstd = torch.empty(T2, dtype=F32, device=x.device)
-        if not K.ln_fwd_twin(x2, w, b, y, y32, mean, rstd, T2, d, eps):
-            K.ln_fwd(x2, w, b, y, mean, rstd, T2, d, eps)
-            y32.copy_(y)
-        ctx.save_for_backward(x2[:T], mean[:T], rstd[:T])
-        ctx.params = (w, b)
-        ctx.in_dtype = x.dtype
-        yf = y.view(*x_full.shape[:-1], d)
-        yf32 = y32.view(*x_full.shape[:-1], d)
+        yf, yf32 = _ln_forward(ctx, x, w, b, eps, x_full, twin=True)
         box.append((yf, yf32))
-        return yf[:B], yf32[:B]
+        return yf[:x.shape[0]], yf32[:x.shape[0]]
 
     @staticmethod
     def backward(ctx, dy, dy32):
@@ -1462,53 +1401,17 @@ class LayerNormPairTwinFn(Function):
 
 class LayerNormPairFn(LayerNormFn):
     """LN of both row sets (a post-LN block's residual output, BERT): bf16 ``Paired``; backward = LayerNormFn's on
-    the base rows."""
+    the base rows, without the rows that ``pos_mask`` spliced in from the source."""
 
     @staticmethod
     def forward(ctx, x, w, b, eps, x_full, box, pos_mask=0):
-        ctx.set_materialize_grads(False)
-        d = x.shape[-1]
-        B = x.shape[0]
-        x2 = _flat2(x_full)
-        T2 = x2.shape[0]
-        T = T2 * B // x_full.shape[0]
-        y = torch.empty(T2, d, dtype=BF16, device=x.device)
-        mean = torch.empty(T2, dtype=F32, device=x.device)
-        rstd = torch.empty(T2, dtype=F32, device=x.device)
-        S = x.shape[1] if x.dim() == 3 else 1
-        if pos_mask:  # whole-position splice of the base rows from the source rows, inside the LN kernel
-            K.ln_fwd_sel(x2, w, b, y, mean, rstd, T2, d, eps, pos_mask, S, T)
-        else:
-            K.ln_fwd(x2, w, b, y, mean, rstd, T2, d, eps)
-        ctx.save_for_backward(x2[:T], mean[:T], rstd[:T])
-        ctx.params = (w, b)
-        ctx.in_dtype = x.dtype
-        ctx.sel = (pos_mask, S)
-        yf = y.view(*x_full.shape[:-1], d)
+        yf, _ = _ln_forward(ctx, x, w, b, eps, x_full, pos_mask=pos_mask)
         box.append(yf)
-        return yf[:B]
+        return yf[:x.shape[0]]
 
     @staticmethod
     def backward(ctx, dy):
-        pos_mask, S = ctx.sel
-        if not pos_mask:
-            return LayerNormFn.backward(ctx, dy) + (None, None, None)
-        if dy is None:
-            return (None,) * 7
-        x2, mean, rstd = ctx.saved_tensors
-        w, b = ctx.params
-        T, d = x2.shape
-        dx = torch.empty(T, d, dtype=F32, device=x2.device)
-        dx16 = torch.empty(T, d, dtype=BF16, device=x2.device) if ctx.in_dtype == F32 else None
-        dw = _grad_slot(w) if w is not None else None
-        db = _grad_slot(b) if b is not None else None
-        K.ln_bwd_sel(_flat2(dy.contiguous()), x2, mean, rstd, w, dx, dw, db, T, d, pos_mask, S, dx16=dx16)
-        _done(w, b)
-        dx = dx.view(*dy.shape[:-1], d)
-        if dx16 is None:
-            return (dx.to(ctx.in_dtype),) + (None,) * 6
-        _set_bf16_twin(dx, dx16)
-        return (dx,) + (None,) * 6
+        return (_ln_backward(ctx, dy, sel=ctx.sel),) + (None,) * 6
 
 
 class QKVPairFn(QKVFn):

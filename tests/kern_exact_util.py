@@ -1,4 +1,5 @@
-"""Helpers shared by the exact tests of the layer-norm, cross-entropy and fused-Adam kernels of csrc/kernels.hip
+"""Helpers shared by the exact tests of the layer-norm kernels of csrc/layer_norm.hip and the cross-entropy and fused-Adam
+kernels of csrc/kernels.hip
 (tests/test_ln_exact.py, tests/test_ce_exact.py and tests/test_adam_exact.py on the GPU, tests/test_kern_exact_ref.py
 on the CPU): float64 references of the same fp32 / bf16 inputs, element-wise bounds built from reference quantities
 alone, operand families, and the perturbations the comparators must flag.
@@ -56,16 +57,17 @@ unique for beta = 0.9 at t = 1, 2, 3 and for beta = 0.999 at t = 1, 2, 3, 10, 10
 from beta^t < 1e-4 on (t = 100 .. 10000) the power is below the resolution of ``1 - beta^t`` and cannot matter.  (The
 bounds started from 4 before the measurement.)
 
-Kernel instantiations of csrc/kernels.hip and a passing case that runs each (GPU modules):
+Kernel instantiations of csrc/layer_norm.hip (``ln_*``; W = 4 the vector layout, W = 1 the fallback) and
+csrc/kernels.hip, and a passing case that runs each (GPU modules):
 
 =========================================  =====================================================================
-ln_fwd_vec_kernel<1,2,3,4,6,8,12,16>       test_ln_exact.py::test_ln_fwd, d = 4 / 252 / 256 ... 4096 (both ends)
-ln_fwd_vec_kernel<*> with y32              test_ln_exact.py::test_ln_fwd (twin checked in every vector case)
-ln_fwd_kernel<4,16,32,64>                  test_ln_fwd, d = 1..255 / 257..1023 / 1025..2047 / 2049..4095, offset view
-ln_bwd_vec_kernel<1..16, f32 / bf16>       test_ln_bwd[plain], same vector d; <*, *, XH16> test_ln_bwd_xh16
-ln_bwd_kernel<4,16,32,64, f32 / bf16>      test_ln_bwd[plain], scalar d and the offset view
-ln_bwd_part_vec_kernel<1..4, *, R = 1>     test_ln_bwd[fused], d <= 1024; test_ln_bwd_long (T = 149, 1021)
-ln_bwd_part_vec_kernel<*, *, R = 2 / 4>    test_launch_variants.py only (IIT_LN_PART_R)
+ln_fwd_kernel<4, 1,2,3,4,6,8,12,16>        test_ln_exact.py::test_ln_fwd, d = 4 / 252 / 256 ... 4096 (both ends)
+ln_fwd_kernel<4, *> with y32               test_ln_exact.py::test_ln_fwd (twin checked in every vector case)
+ln_fwd_kernel<1, 4,16,32,64>               test_ln_fwd, d = 1..255 / 257..1023 / 1025..2047 / 2049..4095, offset view
+ln_bwd_kernel<4, 1..16, f32 / bf16>        test_ln_bwd[plain], same vector d; <4, *, *, XH16> test_ln_bwd_xh16
+ln_bwd_kernel<1, 4,16,32,64, f32 / bf16>   test_ln_bwd[plain], scalar d and the offset view
+ln_bwd_part_kernel<1..4, *, R = 1>         test_ln_bwd[fused], d <= 1024; test_ln_bwd_long (T = 149, 1021)
+ln_bwd_part_kernel<*, *, R = 2 / 4>        test_launch_variants.py only (IIT_LN_PART_R)
 ln_part_reduce_kernel                      test_ln_bwd_long: G = 4 (T = 149: 4-wide loop + rest), G = 32 (T = 1021)
 ln_dwdb_vec_kernel<f32 / bf16>             test_ln_dwdb_vec (IIT_LN_FUSED_DWDB=0, and d > 1024)
 ln_dwdb_kernel<f32 / bf16>                 test_ln_dwdb_scalar (d = 130, T = 257) and scalar d of test_ln_bwd

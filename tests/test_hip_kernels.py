@@ -120,7 +120,7 @@ def test_layernorm(K, d, affine, bf16_dy):
     dres = torch.randn(T, d, device=dev)
     dx = torch.empty(T, d, device=dev)
     dx16 = torch.empty(T, d, dtype=torch.bfloat16, device=dev)
-    # the affine gradients accumulate into the existing slots (fused into the dx pass for d <= 1024, iit_ln_bwd_part)
+    # the affine gradients accumulate into the existing slots (fused into the dx pass for d <= 1024: iit_ln_bwd with a partials buffer)
     dw = torch.ones(d, device=dev) if affine else None
     db = torch.ones(d, device=dev) if affine else None
     K.ln_bwd(g, x, mean, rstd, w, dx, dw, db, T, d, dres=dres, dx16=dx16)

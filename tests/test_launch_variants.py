@@ -1,5 +1,5 @@
 """Kernels that only a launch-time environment variable selects (read once per process, so each needs a fresh one):
-``IIT_LN_PART_R`` = 2 / 4 (``ln_bwd_part_vec_kernel<*, *, 2 / 4>``), ``IIT_ADAM_NT`` = 0 (``adam_span_kernel<false,
+``IIT_LN_PART_R`` = 2 / 4 (``ln_bwd_part_kernel<*, *, 2 / 4>``), ``IIT_ADAM_NT`` = 0 (``adam_span_kernel<false,
 4>``) and ``IIT_ADAM_UNROLL`` = 1 / 2 (``adam_span_kernel<true, 1 / 2>``).  Three child processes, one at a time, each
 with one layer-norm and / or one Adam variable set, run the fused layer-norm backward and row-select cases of
 tests/test_ln_exact.py and the single-step cases of tests/test_adam_exact.py under their own time limit; the loop

@@ -1,9 +1,9 @@
-"""Element-wise layer-norm tests on the GPU: every LN kernel of csrc/kernels.hip, forward and backward, against the
+"""Element-wise layer-norm tests on the GPU: every LN kernel of csrc/layer_norm.hip, forward and backward, against the
 float64 reference and the derived bounds of tests/kern_exact_util.py (proved on the CPU by
 tests/test_kern_exact_ref.py).
 
-* forward (``ln_fwd``, ``ln_fwd_twin``): every ``d`` at both ends of each vector (V4 = 1 .. 16) and scalar
-  (VPL = 4 .. 64) instantiation, a misaligned view that sends a ``d % 4 == 0`` row to the scalar kernels, T = 1, 3, 5,
+* forward (``ln_fwd``, ``ln_fwd_twin``): every ``d`` at both ends of each vector (W = 4, N = 1 .. 16) and scalar
+  (W = 1, N = 4 .. 64) instantiation, a misaligned view that sends a ``d % 4 == 0`` row to the scalar kernels, T = 1, 3, 5,
   9 (partial last workgroup), four operand families, with and without affine parameters; d = 4097 / 4100 refused;
 * backward (``ln_bwd`` fused-partials and plain paths, ``ln_bwd_xh16``): fp32 / bf16 dy, dres, dx16, accumulate, dy2
   (in-kernel and summed by the wrapper), prefilled dw / db; the long-row-count cases of the partial reduce and of the
