@@ -585,6 +585,91 @@ def _packed3(a: Optional[torch.Tensor], b: Optional[torch.Tensor], c: Optional[t
     return b.data_ptr() == a.data_ptr() + n * es and c.data_ptr() == a.data_ptr() + 2 * n * es
 
 
+# ---- the projection Functions (QKV, linear / unembed, MLP in, MLP out): one forward per op, shared by the unpaired
+# class and its paired twin the way _ln_forward is, and one weight-gradient tail for the four backwards.
+def _rows_bf16(x, x_full):
+    """(the rows an op computes over -- ``x``, or ``x_full`` (base rows first, then the source rows) for the paired
+    classes -- as bf16 [T2, K], the number of base rows)."""
+    rows = x if x_full is None else x_full
+    x2 = _flat2(rows.to(BF16).contiguous())
+    return x2, x2.shape[0] * x.shape[0] // rows.shape[0]
+
+
+def _base_rows(t2, T: int):
+    """The base rows of a [T2, n] buffer: what a projection saves for its backward (source rows get no gradient)."""
+    return t2 if t2.shape[0] == T else t2[:T]
+
+
+def _wgrad_slots(layout_ok: bool, *Ws):
+    """``(store, gradients of Ws)`` for a backward whose one GEMM writes the complete gradient of ``Ws``: claimed for
+    a store when the arena allows it (:func:`_claim_store`; never asked when ``layout_ok``, the op's condition on the
+    parameters' layout, fails), else ready to be accumulated into (None for a frozen parameter)."""
+    store = layout_ok and _claim_store(*Ws)
+    return store, [W.grad if store else _grad_slot(W) for W in Ws]
+
+
+def _wgrad_rows(gW, Kd: int, N: int):
+    """``(gW as [Kd][N] rows, its row stride)`` for the weight-gradient GEMM; (None, 0) without a gradient."""
+    if gW is None:
+        return None, 0
+    gW2 = gW.reshape(Kd, N) if gW.is_contiguous() else gW
+    assert gW2.stride(-1) == 1 and gW2.dim() == 2, "weight gradient must have unit column stride"
+    return gW2, gW2.stride(0)
+
+
+def _wgrad_tail(ctx, xspec, x2, g2, ldg, Ws, C, ldc, store, gb):
+    """The GEMMs of a projection's backward: the weight gradient ``C (+)= x2^T g2`` (``C``: the gradient of ``Ws`` as
+    [K][N] rows of stride ``ldc``, or None; stored when ``store``, see :func:`_wgrad_slots`) and the input gradient
+    ``xspec`` (a :func:`gemm` keyword dict, or None) -- as a pair, which may share one dual launch and prefetches the
+    operands of the pair that runs next, when there are both.  The weight-gradient GEMM also adds the bias gradient
+    ``colsum(g2)`` into ``gb`` where :func:`_fused_bias` allows it and the sums of squares of a stored gradient into
+    the arena's norm slots.  Returns the bias slot it summed into (None: the sum is still to be done)."""
+    bs = None
+    if C is not None:
+        T, N = g2.shape
+        bs = _fused_bias(gb, N)
+        wspec = dict(A=x2, B=g2, C=C, M=x2.shape[1], N=N, K=T, lda=x2.shape[1], ldb=ldg, ldc=ldc,
+                     mode=K.MODE_AKM | K.MODE_BKM, epi=K.EPI_F32_STORE if store else K.EPI_F32_ACC, fresh=store,
+                     bsum=bs, gsq=_norm_slots(store, *Ws))
+        choice = gemm_pair(xspec, wspec, prefetch=_pf_next(ctx)) if xspec is not None else gemm(**wspec)
+        if store:
+            _settle_claim(choice, *Ws)
+    elif xspec is not None:
+        gemm(**xspec)
+    return bs
+
+
+def _bias_tail(bs, gb, g2, ldg, bias, Ws) -> None:
+    """After :func:`_wgrad_tail`: queue the bias gradient ``gb += colsum(g2)`` unless the weight-gradient GEMM summed
+    it (``bs``) or there is none to sum (no slot, or an earlier epilogue did it), then report ``bias`` and ``Ws`` to
+    the data-parallel reducer, the biases first (queued ones are reported when their sums land)."""
+    if gb is not None and bs is None:
+        _BIAS_SUMS.add(g2, ldg, gb, g2.shape[0], gb.numel(), *bias)
+    else:
+        _done(*bias)
+    _done(*Ws)
+
+
+def _qkv_forward(ctx, x, layer, bias_bf16, W_Q, W_K, W_V, b_Q, b_K, b_V, x_full=None):
+    """Forward of QKVFn / QKVPairFn: packed qkv [*, S, 3, H, dh] of every row; the base rows are saved."""
+    ctx.set_materialize_grads(False)
+    B, S, d = x.shape
+    H, dh = W_Q.shape[0], W_Q.shape[2]
+    HD = H * dh
+    x2, T = _rows_bf16(x, x_full)
+    T2 = x2.shape[0]
+    out = torch.empty(T2 // S, S, 3, H, dh, dtype=BF16, device=x.device)
+    gemm(x2, layer["qkv"], out, M=T2, N=3 * HD, K=d, lda=d, ldb=3 * HD, ldc=3 * HD, mode=K.MODE_BKM,
+         epi=K.EPI_BF16_BIAS3, bias0=b_Q, bias1=b_K, bias2=b_V, bias_cols=HD, blas_bias=bias_bf16)
+    xb = _base_rows(x2, T)
+    ctx.save_for_backward(xb)
+    ctx.layer = layer
+    ctx.params = (W_Q, W_K, W_V, b_Q, b_K, b_V)
+    ctx.dims = (B, S, d, H, dh)
+    _pf_register(ctx, xb, layer["qkv"])
+    return out
+
+
 class QKVFn(Function):
     """x [B,S,d] bf16 -> packed qkv [B,S,3,H,dh] bf16 (bias fused); weights from the packed [d][3HD] shadow.
 
@@ -593,21 +678,7 @@ class QKVFn(Function):
 
     @staticmethod
     def forward(ctx, x, layer, bias_bf16, W_Q, W_K, W_V, b_Q, b_K, b_V):
-        ctx.set_materialize_grads(False)
-        B, S, d = x.shape
-        H, dh = W_Q.shape[0], W_Q.shape[2]
-        HD = H * dh
-        x2 = _flat2(x.to(BF16).contiguous())
-        T = x2.shape[0]
-        out = torch.empty(B, S, 3, H, dh, dtype=BF16, device=x.device)
-        gemm(x2, layer["qkv"], out, M=T, N=3 * HD, K=d, lda=d, ldb=3 * HD, ldc=3 * HD, mode=K.MODE_BKM,
-             epi=K.EPI_BF16_BIAS3, bias0=b_Q, bias1=b_K, bias2=b_V, bias_cols=HD, blas_bias=bias_bf16)
-        ctx.save_for_backward(x2)
-        ctx.layer = layer
-        ctx.params = (W_Q, W_K, W_V, b_Q, b_K, b_V)
-        ctx.dims = (B, S, d, H, dh)
-        _pf_register(ctx, x2, layer["qkv"])
-        return out
+        return _qkv_forward(ctx, x, layer, bias_bf16, W_Q, W_K, W_V, b_Q, b_K, b_V)
 
     @staticmethod
     def backward(ctx, dqkv):
@@ -621,39 +692,23 @@ class QKVFn(Function):
         g = dqkv.to(BF16).contiguous().view(T, 3 * HD)
         dx = torch.empty(T, d, dtype=BF16, device=g.device)
         xspec = dict(A=g, B=ctx.layer["qkv"], C=dx, M=T, N=d, K=3 * HD, lda=3 * HD, ldb=3 * HD, ldc=d, epi=K.EPI_BF16)
-        store = W_Q.stride() == (dh, 3 * HD, 1) and _packed3(W_Q, W_K, W_V, HD) and \
-            _claim_store(W_Q, W_K, W_V)
-        if store:
-            gq, gk, gv = W_Q.grad, W_K.grad, W_V.grad
-        else:
-            gq, gk, gv = _grad_slot(W_Q), _grad_slot(W_K), _grad_slot(W_V)
+        Ws = (W_Q, W_K, W_V)
+        store, (gq, gk, gv) = _wgrad_slots(W_Q.stride() == (dh, 3 * HD, 1) and _packed3(W_Q, W_K, W_V, HD), *Ws)
         gbs = [_grad_slot(bp) for bp in (b_Q, b_K, b_V)]
-        packed_b = all(gb is not None for gb in gbs) and all(gb.is_contiguous() for gb in gbs) and _packed3(*gbs, HD)
-        bs = None
-        if gq is not None and gk is not None and gv is not None and gq.stride() == (dh, 3 * HD, 1) and \
-                _packed3(gq, gk, gv, HD):
-            if packed_b:  # b_Q | b_K | b_V gradients are one [3 HD] run: the GEMM adds colsum(dqkv) into it
-                bs = _fused_bias(torch.as_strided(gbs[0], (3 * HD,), (1,)), 3 * HD)
-            choice = gemm_pair(xspec, dict(A=x2, B=g, C=gq, M=d, N=3 * HD, K=T, lda=d, ldb=3 * HD, ldc=3 * HD,
-                                           mode=K.MODE_AKM | K.MODE_BKM,
-                                           epi=K.EPI_F32_STORE if store else K.EPI_F32_ACC, fresh=store, bsum=bs,
-                                           gsq=_norm_slots(store, W_Q, W_K, W_V)), prefetch=_pf_next(ctx))
-            if store:
-                _settle_claim(choice, W_Q, W_K, W_V)
-        else:
-            gemm(**xspec)
-            if gq is not None and gk is not None and gv is not None:
-                gemm(x2, g, gq, C2=gk, C3=gv, M=d, N=3 * HD, K=T, lda=d, ldb=3 * HD, ldc=0,
-                     mode=K.MODE_AKM | K.MODE_BKM, epi=K.EPI_F32_ACC_QKV, qkv=(dh, H, d))
-        if all(gb is not None for gb in gbs):
-            if bs is not None:
-                _done(b_Q, b_K, b_V)  # summed by the weight-gradient GEMM
-            elif packed_b:
-                _BIAS_SUMS.add(g, 3 * HD, gbs[0], T, 3 * HD, b_Q, b_K, b_V)
-            else:
-                K.colsum3_accum(g, 3 * HD, gbs, T, HD)
-                _done(b_Q, b_K, b_V)
-        _done(W_Q, W_K, W_V)
+        have_b = all(s is not None for s in gbs)
+        # b_Q | b_K | b_V gradients that are one [3 HD] run take the fused (or the queued) column sum of dqkv
+        gb = None
+        if have_b and all(s.is_contiguous() for s in gbs) and _packed3(*gbs, HD):
+            gb = torch.as_strided(gbs[0], (3 * HD,), (1,))
+        have_w = gq is not None and gk is not None and gv is not None
+        packed_w = have_w and gq.stride() == (dh, 3 * HD, 1) and _packed3(gq, gk, gv, HD)
+        bs = _wgrad_tail(ctx, xspec, x2, g, 3 * HD, Ws, gq if packed_w else None, 3 * HD, store, gb)
+        if have_w and not packed_w:  # three separate gradients: the scatter epilogue
+            gemm(x2, g, gq, C2=gk, C3=gv, M=d, N=3 * HD, K=T, lda=d, ldb=3 * HD, ldc=0,
+                 mode=K.MODE_AKM | K.MODE_BKM, epi=K.EPI_F32_ACC_QKV, qkv=(dh, H, d))
+        if have_b and gb is None:
+            K.colsum3_accum(g, 3 * HD, gbs, T, HD)
+        _bias_tail(bs, gb, g, 3 * HD, (b_Q, b_K, b_V) if have_b else (), Ws)
         return (dx.view(B, S, d),) + (None,) * 8
 
 
@@ -986,6 +1041,46 @@ def llama_fused_ok(x: torch.Tensor) -> bool:
     return x.is_cuda and x.dtype == BF16 and os.environ.get("IIT_LLAMA_FUSED", "1") != "0"
 
 
+def _resid_rows(resid, resid_full):
+    """The fp32 residual rows [T2, N] that go with :func:`_rows_bf16`'s."""
+    return _flat2((resid if resid_full is None else resid_full).float().contiguous())
+
+
+def _linear_forward(ctx, x, W, b, w, ldw, resid, out_kind, x_full=None, resid_full=None):
+    """Forward of LinearFn / UnembedFn / LinearPairFn: the output of every row in the rows' leading shape; the base
+    rows are saved."""
+    ctx.set_materialize_grads(False)
+    lead = (x if x_full is None else x_full).shape[:-1]
+    Kd = x.shape[-1]
+    N = W.shape[-1]
+    x2, T = _rows_bf16(x, x_full)
+    T2 = x2.shape[0]
+    dev = x.device
+    if out_kind == "bf16":
+        out = torch.empty(T2, N, dtype=BF16, device=dev)
+        gemm(x2, w, out, M=T2, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=N, mode=K.MODE_BKM, epi=K.EPI_BF16, bias0=b)
+        res = out.view(*lead, N)
+    elif out_kind == "f32":
+        Np = _pad8(N)
+        out = torch.empty(T2, Np, dtype=F32, device=dev)
+        gemm(x2, w, out, M=T2, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=Np, mode=K.MODE_BKM, epi=K.EPI_F32_STORE, bias0=b)
+        res = out[:, :N]
+        res = res.unflatten(0, lead) if len(lead) != 1 else res
+    else:
+        out = torch.empty(T2, N, dtype=F32, device=dev)
+        gemm(x2, w, out, M=T2, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=N, mode=K.MODE_BKM, epi=K.EPI_F32_RESID, bias0=b,
+             resid=_resid_rows(resid, resid_full), ldr=N)
+        res = out.view(*lead, N)
+    xb = _base_rows(x2, T)
+    ctx.save_for_backward(xb)
+    ctx.params = (W, b)
+    ctx.w = w
+    _pf_register(ctx, xb, w)
+    ctx.ldw = ldw
+    ctx.meta = (x.shape[:-1], Kd, N, out_kind, x.dtype)
+    return res
+
+
 class LinearFn(Function):
     """y = x @ W + b, TL-layout master W [K, N] with bf16 shadow ``w`` (row stride ``ldw``).
 
@@ -994,36 +1089,7 @@ class LinearFn(Function):
 
     @staticmethod
     def forward(ctx, x, W, b, w, ldw, resid, out_kind):
-        ctx.set_materialize_grads(False)
-        lead = x.shape[:-1]
-        Kd = x.shape[-1]
-        N = W.shape[-1]
-        x2 = _flat2(x.to(BF16).contiguous())
-        T = x2.shape[0]
-        dev = x.device
-        if out_kind == "bf16":
-            out = torch.empty(T, N, dtype=BF16, device=dev)
-            gemm(x2, w, out, M=T, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=N, mode=K.MODE_BKM, epi=K.EPI_BF16, bias0=b)
-            res = out.view(*lead, N)
-        elif out_kind == "f32":
-            Np = _pad8(N)
-            out = torch.empty(T, Np, dtype=F32, device=dev)
-            gemm(x2, w, out, M=T, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=Np, mode=K.MODE_BKM, epi=K.EPI_F32_STORE, bias0=b)
-            res = out[:, :N]
-            res = res.unflatten(0, lead) if len(lead) != 1 else res
-        else:
-            r2 = _flat2(resid.float().contiguous())
-            out = torch.empty(T, N, dtype=F32, device=dev)
-            gemm(x2, w, out, M=T, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=N, mode=K.MODE_BKM, epi=K.EPI_F32_RESID, bias0=b,
-                 resid=r2, ldr=N)
-            res = out.view(*lead, N)
-        ctx.save_for_backward(x2)
-        ctx.params = (W, b)
-        ctx.w = w
-        _pf_register(ctx, x2, w)
-        ctx.ldw = ldw
-        ctx.meta = (lead, Kd, N, out_kind, x.dtype)
-        return res
+        return _linear_forward(ctx, x, W, b, w, ldw, resid, out_kind)
 
     @staticmethod
     def backward(ctx, gy):
@@ -1052,30 +1118,12 @@ class LinearFn(Function):
                 gemm(g2, ctx.w, dxf, M=T, N=Kd, K=N, lda=ldg, ldb=ctx.ldw, ldc=Kd, mode=amode, epi=K.EPI_F32_ACC,
                      splits=splits)
                 dx = dxf.to(x_dtype).view(*lead, Kd)
-        store = _claim_store(W)
-        gW = W.grad if store else _grad_slot(W)
+        store, (gW,) = _wgrad_slots(True, W)
         gb = _grad_slot(b)
-        bs = _fused_bias(gb, N) if gW is not None else None
-        if gW is not None:
-            mode = K.MODE_AKM | K.MODE_BKM
-            gW2 = gW.reshape(Kd, N) if gW.is_contiguous() else gW
-            assert gW2.stride(-1) == 1 and gW2.dim() == 2, "weight gradient must have unit column stride"
-            wspec = dict(A=x2, B=g2, C=gW2, M=Kd, N=N, K=T, lda=Kd, ldb=ldg, ldc=gW2.stride(0), mode=mode,
-                         epi=K.EPI_F32_STORE if store else K.EPI_F32_ACC, fresh=store, bsum=bs,
-                         gsq=_norm_slots(store, W))
-            choice = gemm_pair(xspec, wspec, prefetch=_pf_next(ctx)) if xspec is not None else gemm(**wspec)
-            if store:
-                _settle_claim(choice, W)
-        elif xspec is not None:
-            gemm(**xspec)
+        bs = _wgrad_tail(ctx, xspec, x2, g2, ldg, (W,), *_wgrad_rows(gW, Kd, N), store, gb)
         if dxb is not None:
             dx = (dxb if x_dtype == BF16 else dxb.to(x_dtype)).view(*lead, Kd)
-        if gb is not None:
-            if bs is not None:
-                _done(b)  # summed by the weight-gradient GEMM
-            else:
-                _BIAS_SUMS.add(g2, ldg, gb, T, N, b)
-        _done(W)
+        _bias_tail(bs, gb, g2, ldg, (b,), (W,))
         return dx, None, None, None, None, gres, None
 
 
@@ -1099,28 +1147,38 @@ class UnembedFn(LinearFn):
         return LinearFn.backward(ctx, gy)[:5]
 
 
+def _mlp_in_forward(ctx, x, W_in, b_in, w, erf, x_full=None, spec=None):
+    """Forward of MLPInFn / MLPInPairFn: ``(pre, post)`` of every row in the rows' leading shape, the base rows of
+    ``post`` spliced from the source rows at ``spec``; the base rows of ``x`` and ``pre`` are saved."""
+    ctx.set_materialize_grads(False)
+    ctx.erf = erf
+    ctx.zero_spec = spec
+    lead = (x if x_full is None else x_full).shape[:-1]
+    d = x.shape[-1]
+    dm = W_in.shape[1]
+    x2, T = _rows_bf16(x, x_full)
+    T2 = x2.shape[0]
+    post = torch.empty(T2, dm, dtype=BF16, device=x.device)
+    pre = torch.empty(T2, dm, dtype=BF16, device=x.device)
+    gemm(x2, w, post, C2=pre, M=T2, N=dm, K=d, lda=d, ldb=dm, ldc=dm, ldc2=dm, mode=K.MODE_BKM,
+         epi=K.EPI_GELU_ERF if erf else K.EPI_GELU, bias0=b_in)
+    if spec is not None:
+        K.sparse_pair(post, T, dm, spec.ptr, 0)
+    xb = _base_rows(x2, T)
+    ctx.save_for_backward(xb, _base_rows(pre, T))
+    ctx.params = (W_in, b_in)
+    ctx.w = w
+    _pf_register(ctx, xb, w)
+    ctx.meta = (x.shape[:-1], d, dm)
+    return pre.view(*lead, dm), post.view(*lead, dm)
+
+
 class MLPInFn(Function):
     """(pre, post) = (x @ W_in + b_in, gelu_new(pre)) in one GEMM epilogue."""
 
     @staticmethod
     def forward(ctx, x, W_in, b_in, w, erf=False):
-        ctx.set_materialize_grads(False)
-        ctx.erf = erf
-        lead = x.shape[:-1]
-        d = x.shape[-1]
-        dm = W_in.shape[1]
-        x2 = _flat2(x.to(BF16).contiguous())
-        T = x2.shape[0]
-        post = torch.empty(T, dm, dtype=BF16, device=x.device)
-        pre = torch.empty(T, dm, dtype=BF16, device=x.device)
-        gemm(x2, w, post, C2=pre, M=T, N=dm, K=d, lda=d, ldb=dm, ldc=dm, ldc2=dm, mode=K.MODE_BKM, epi=K.EPI_GELU_ERF if erf else K.EPI_GELU,
-             bias0=b_in)
-        ctx.save_for_backward(x2, pre)
-        ctx.params = (W_in, b_in)
-        ctx.w = w
-        _pf_register(ctx, x2, w)
-        ctx.meta = (lead, d, dm)
-        return pre.view(*lead, dm), post.view(*lead, dm)
+        return _mlp_in_forward(ctx, x, W_in, b_in, w, erf)
 
     @staticmethod
     def backward(ctx, gpre, gpost):
@@ -1142,25 +1200,11 @@ class MLPInFn(Function):
             dpre = gpre.to(BF16).contiguous().view(T, dm)
         dx = torch.empty(T, d, dtype=BF16, device=x2.device)
         xspec = dict(A=dpre, B=ctx.w, C=dx, M=T, N=d, K=dm, lda=dm, ldb=dm, ldc=d, epi=K.EPI_BF16)
-        store = W_in.is_contiguous() and _claim_store(W_in)
-        gW = W_in.grad if store else _grad_slot(W_in)
+        store, (gW,) = _wgrad_slots(W_in.is_contiguous(), W_in)
         summed = _bias_sum_done(gpre if gpost is None else None, b_in)  # by MLPOutGeluFn's DGELU epilogue
         gb = None if summed else _grad_slot(b_in)
-        bs = _fused_bias(gb, dm) if gW is not None else None
-        if gW is not None:
-            choice = gemm_pair(xspec, dict(A=x2, B=dpre, C=gW, M=d, N=dm, K=T, lda=d, ldb=dm, ldc=dm,
-                                           mode=K.MODE_AKM | K.MODE_BKM,
-                                           epi=K.EPI_F32_STORE if store else K.EPI_F32_ACC, fresh=store, bsum=bs,
-                                           gsq=_norm_slots(store, W_in)), prefetch=_pf_next(ctx))
-            if store:
-                _settle_claim(choice, W_in)
-        else:
-            gemm(**xspec)
-        if gb is not None and bs is None:
-            _BIAS_SUMS.add(dpre, dm, gb, T, dm, b_in)
-        else:
-            _done(b_in)
-        _done(W_in)
+        bs = _wgrad_tail(ctx, xspec, x2, dpre, dm, (W_in,), gW, dm, store, gb)
+        _bias_tail(bs, gb, dpre, dm, (b_in,), (W_in,))
         return dx.view(*lead, d), None, None, None, None
 
 
@@ -1169,6 +1213,29 @@ def _bias_sum_done(g: Optional[torch.Tensor], b: Optional[torch.Tensor]) -> bool
     epilogue); the tag is checked against the tensor's storage and version, like the bf16 twin."""
     tag = getattr(g, "_iit_bias_sum", None) if g is not None else None
     return tag is not None and b is not None and tag == (g.data_ptr(), g._version, id(b))
+
+
+def _mlp_out_forward(ctx, pre, post, W, b, w, ldw, resid, b_in, erf, post_full=None, resid_full=None):
+    """Forward of MLPOutGeluFn / MLPOutGeluPairFn: the output of every row (``post`` as it comes, uncast) in the
+    rows' leading shape; the base rows of ``post`` and ``pre`` are saved."""
+    ctx.set_materialize_grads(False)
+    ctx.erf = erf
+    rows = post if post_full is None else post_full
+    Kd = post.shape[-1]
+    N = W.shape[-1]
+    x2 = _flat2(rows)
+    T2 = x2.shape[0]
+    out = torch.empty(T2, N, dtype=F32, device=post.device)
+    gemm(x2, w, out, M=T2, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=N, mode=K.MODE_BKM, epi=K.EPI_F32_RESID, bias0=b,
+         resid=_resid_rows(resid, resid_full), ldr=N)
+    xb = _base_rows(x2, T2 * post.shape[0] // rows.shape[0])
+    ctx.save_for_backward(xb, _flat2(pre))
+    ctx.params = (W, b, b_in)
+    ctx.w = w
+    _pf_register(ctx, xb, w)
+    ctx.ldw = ldw
+    ctx.meta = (post.shape[:-1], Kd, N)
+    return out.view(*rows.shape[:-1], N)
 
 
 class MLPOutGeluFn(Function):
@@ -1183,24 +1250,7 @@ class MLPOutGeluFn(Function):
 
     @staticmethod
     def forward(ctx, pre, post, W, b, w, ldw, resid, b_in, erf=False):
-        ctx.set_materialize_grads(False)
-        ctx.erf = erf
-        lead = post.shape[:-1]
-        Kd = post.shape[-1]
-        N = W.shape[-1]
-        x2 = _flat2(post)
-        T = x2.shape[0]
-        r2 = _flat2(resid.float().contiguous())
-        out = torch.empty(T, N, dtype=F32, device=post.device)
-        gemm(x2, w, out, M=T, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=N, mode=K.MODE_BKM, epi=K.EPI_F32_RESID, bias0=b,
-             resid=r2, ldr=N)
-        ctx.save_for_backward(x2, _flat2(pre))
-        ctx.params = (W, b, b_in)
-        ctx.w = w
-        _pf_register(ctx, x2, w)
-        ctx.ldw = ldw
-        ctx.meta = (lead, Kd, N)
-        return out.view(*lead, N)
+        return _mlp_out_forward(ctx, pre, post, W, b, w, ldw, resid, b_in, erf)
 
     @staticmethod
     def backward(ctx, gy):
@@ -1219,31 +1269,14 @@ class MLPOutGeluFn(Function):
             gbi = _grad_slot(b_in)
             xspec = dict(A=g2, B=ctx.w, C=dpre, M=T, N=Kd, K=N, lda=ldg, ldb=ctx.ldw, ldc=Kd, mode=K.MODE_NN,
                          epi=K.EPI_DGELU_ERF if ctx.erf else K.EPI_DGELU, aux=pre2, ldc2=pre2.stride(0), colsum=gbi)
-        store = _claim_store(W)
-        gW = W.grad if store else _grad_slot(W)
+        store, (gW,) = _wgrad_slots(True, W)
         gb = _grad_slot(b)
-        bs = _fused_bias(gb, N) if gW is not None else None
-        if gW is not None:
-            gW2 = gW.reshape(Kd, N) if gW.is_contiguous() else gW
-            assert gW2.stride(-1) == 1 and gW2.dim() == 2, "weight gradient must have unit column stride"
-            wspec = dict(A=x2, B=g2, C=gW2, M=Kd, N=N, K=T, lda=Kd, ldb=ldg, ldc=gW2.stride(0),
-                         mode=K.MODE_AKM | K.MODE_BKM, epi=K.EPI_F32_STORE if store else K.EPI_F32_ACC, fresh=store,
-                         bsum=bs, gsq=_norm_slots(store, W))
-            choice = gemm_pair(xspec, wspec, prefetch=_pf_next(ctx)) if xspec is not None else gemm(**wspec)
-            if store:
-                _settle_claim(choice, W)
-        elif xspec is not None:
-            gemm(**xspec)
+        bs = _wgrad_tail(ctx, xspec, x2, g2, ldg, (W,), *_wgrad_rows(gW, Kd, N), store, gb)
         if dpre is not None:
             dpre = dpre.view(*lead, Kd)
             if gbi is not None:
                 dpre._iit_bias_sum = (dpre.data_ptr(), dpre._version, id(b_in))
-        if gb is not None:
-            if bs is not None:
-                _done(b)  # summed by the weight-gradient GEMM
-            else:
-                _BIAS_SUMS.add(g2, ldg, gb, T, N, b)
-        _done(W)
+        _bias_tail(bs, gb, g2, ldg, (b,), (W,))
         return dpre, None, None, None, None, None, gy, None, None
 
 
@@ -1417,23 +1450,9 @@ class LayerNormPairFn(LayerNormFn):
 class QKVPairFn(QKVFn):
     @staticmethod
     def forward(ctx, x, layer, bias_bf16, W_Q, W_K, W_V, b_Q, b_K, b_V, x_full, box):
-        ctx.set_materialize_grads(False)
-        B, S, d = x.shape
-        B2 = x_full.shape[0]
-        H, dh = W_Q.shape[0], W_Q.shape[2]
-        HD = H * dh
-        x2 = _flat2(x_full)
-        T2 = x2.shape[0]
-        out = torch.empty(B2, S, 3, H, dh, dtype=BF16, device=x.device)
-        gemm(x2, layer["qkv"], out, M=T2, N=3 * HD, K=d, lda=d, ldb=3 * HD, ldc=3 * HD, mode=K.MODE_BKM,
-             epi=K.EPI_BF16_BIAS3, bias0=b_Q, bias1=b_K, bias2=b_V, bias_cols=HD, blas_bias=bias_bf16)
-        ctx.save_for_backward(x2[:B * S])
-        ctx.layer = layer
-        ctx.params = (W_Q, W_K, W_V, b_Q, b_K, b_V)
-        ctx.dims = (B, S, d, H, dh)
-        _pf_register(ctx, x2[:B * S], layer["qkv"])
+        out = _qkv_forward(ctx, x, layer, bias_bf16, W_Q, W_K, W_V, b_Q, b_K, b_V, x_full)
         box.append(out)
-        return out[:B]
+        return out[:x.shape[0]]
 
     @staticmethod
     def backward(ctx, dqkv):
@@ -1505,31 +1524,9 @@ class LinearPairFn(LinearFn):
 
     @staticmethod
     def forward(ctx, x, W, b, w, ldw, resid, out_kind, x_full, resid_full, box):
-        ctx.set_materialize_grads(False)
-        B = x.shape[0]
-        lead = x.shape[:-1]
-        Kd = x.shape[-1]
-        N = W.shape[-1]
-        x2 = _flat2(x_full)
-        T2 = x2.shape[0]
-        T = T2 * B // x_full.shape[0]
-        if out_kind == "bf16":
-            out = torch.empty(T2, N, dtype=BF16, device=x.device)
-            gemm(x2, w, out, M=T2, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=N, mode=K.MODE_BKM, epi=K.EPI_BF16, bias0=b)
-        else:
-            r2 = _flat2(resid_full)
-            out = torch.empty(T2, N, dtype=F32, device=x.device)
-            gemm(x2, w, out, M=T2, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=N, mode=K.MODE_BKM, epi=K.EPI_F32_RESID, bias0=b,
-                 resid=r2, ldr=N)
-        ctx.save_for_backward(x2[:T])
-        ctx.params = (W, b)
-        ctx.w = w
-        _pf_register(ctx, x2[:T], w)
-        ctx.ldw = ldw
-        ctx.meta = (lead, Kd, N, out_kind, x.dtype)
-        of = out.view(*x_full.shape[:-1], N)
+        of = _linear_forward(ctx, x, W, b, w, ldw, resid, out_kind, x_full, resid_full)
         box.append(of)
-        return of[:B]
+        return of[:x.shape[0]]
 
     @staticmethod
     def backward(ctx, gy):
@@ -1545,30 +1542,9 @@ class MLPInPairFn(MLPInFn):
 
     @staticmethod
     def forward(ctx, x, W_in, b_in, w, erf, x_full, spec, box):
-        ctx.set_materialize_grads(False)
-        ctx.erf = erf
-        ctx.zero_spec = spec
-        B = x.shape[0]
-        lead = x.shape[:-1]
-        d = x.shape[-1]
-        dm = W_in.shape[1]
-        x2 = _flat2(x_full)
-        T2 = x2.shape[0]
-        T = T2 * B // x_full.shape[0]
-        post = torch.empty(T2, dm, dtype=BF16, device=x.device)
-        pre = torch.empty(T2, dm, dtype=BF16, device=x.device)
-        gemm(x2, w, post, C2=pre, M=T2, N=dm, K=d, lda=d, ldb=dm, ldc=dm, ldc2=dm, mode=K.MODE_BKM,
-             epi=K.EPI_GELU_ERF if erf else K.EPI_GELU, bias0=b_in)
-        if spec is not None:
-            K.sparse_pair(post, T, dm, spec.ptr, 0)
-        ctx.save_for_backward(x2[:T], pre[:T])
-        ctx.params = (W_in, b_in)
-        ctx.w = w
-        _pf_register(ctx, x2[:T], w)
-        ctx.meta = (lead, d, dm)
-        pf, qf = pre.view(*x_full.shape[:-1], dm), post.view(*x_full.shape[:-1], dm)
+        pf, qf = _mlp_in_forward(ctx, x, W_in, b_in, w, erf, x_full, spec)
         box.append((pf, qf))
-        return pf[:B], qf[:B]
+        return pf[:x.shape[0]], qf[:x.shape[0]]
 
     @staticmethod
     def backward(ctx, gpre, gpost):
@@ -1578,28 +1554,9 @@ class MLPInPairFn(MLPInFn):
 class MLPOutGeluPairFn(MLPOutGeluFn):
     @staticmethod
     def forward(ctx, pre, post, W, b, w, ldw, resid, b_in, erf, post_full, resid_full, box):
-        ctx.set_materialize_grads(False)
-        ctx.erf = erf
-        B = post.shape[0]
-        lead = post.shape[:-1]
-        Kd = post.shape[-1]
-        N = W.shape[-1]
-        x2 = _flat2(post_full)
-        T2 = x2.shape[0]
-        T = T2 * B // post_full.shape[0]
-        r2 = _flat2(resid_full)
-        out = torch.empty(T2, N, dtype=F32, device=post.device)
-        gemm(x2, w, out, M=T2, N=N, K=Kd, lda=Kd, ldb=ldw, ldc=N, mode=K.MODE_BKM, epi=K.EPI_F32_RESID, bias0=b,
-             resid=r2, ldr=N)
-        ctx.save_for_backward(x2[:T], _flat2(pre))
-        ctx.params = (W, b, b_in)
-        ctx.w = w
-        _pf_register(ctx, x2[:T], w)
-        ctx.ldw = ldw
-        ctx.meta = (lead, Kd, N)
-        of = out.view(*post_full.shape[:-1], N)
+        of = _mlp_out_forward(ctx, pre, post, W, b, w, ldw, resid, b_in, erf, post_full, resid_full)
         box.append(of)
-        return of[:B]
+        return of[:post.shape[0]]
 
     @staticmethod
     def backward(ctx, gy):
