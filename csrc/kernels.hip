@@ -28,10 +28,25 @@ __global__ void embed_pos_fwd_kernel(const long* __restrict__ tok, const float* 
   }
 }
 
+// d % 4 != 0, or rows that are not 16-byte aligned: one column per thread
+__global__ void embed_pos_fwd_scalar_kernel(const long* __restrict__ tok, const float* __restrict__ WE,
+                                            const float* __restrict__ Wpos, float* __restrict__ out, int T, int S,
+                                            int d) {
+  const int t = blockIdx.x;
+  if (t >= T) return;
+  const float* e = WE + tok[t] * (long)d;
+  const float* p = Wpos + (long)(t % S) * d;
+  float* o = out + (long)t * d;
+  for (int i = threadIdx.x; i < d; i += blockDim.x) o[i] = e[i] + p[i];
+}
+
 IIT_EXPORT int iit_embed_pos_fwd(const long* tok, const float* WE, const float* Wpos, float* out, int T, int S,
                                  int d, void* stream) {
-  hipLaunchKernelGGL(embed_pos_fwd_kernel, dim3(T), dim3(d >= 256 ? 64 : 64), 0, (hipStream_t)stream, tok, WE, Wpos,
-                     out, T, S, d);
+  if (d % 4 == 0 && ((((uintptr_t)WE) | ((uintptr_t)Wpos) | ((uintptr_t)out)) & 15) == 0)
+    hipLaunchKernelGGL(embed_pos_fwd_kernel, dim3(T), dim3(64), 0, (hipStream_t)stream, tok, WE, Wpos, out, T, S, d);
+  else
+    hipLaunchKernelGGL(embed_pos_fwd_scalar_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, tok, WE, Wpos, out,
+                       T, S, d);
   return hipGetLastError();
 }
 
@@ -954,13 +969,9 @@ IIT_EXPORT int iit_colsum_accum(const void* x, int f32, long ld, float* out, int
   return hipGetLastError();
 }
 
-// out = gelu_new(pre)  (bf16 -> bf16, strided rows; 8 elements / 16 B per thread when aligned)
-__device__ __forceinline__ float gelu_new_fast(float x) {
-  // tanh(u) = 1 - 2 / (exp(2u) + 1): one exp + one fast reciprocal instead of libm tanhf
-  const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-  const float t = 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * u) + 1.f);
-  return 0.5f * x * (1.f + t);
-}
+// out = gelu(pre)  (bf16 -> bf16, strided rows; 8 elements / 16 B per thread when aligned).  gelu_new is gelu_new_f of
+// common.h, the formula of the fused GEMM epilogues these kernels stand in for: its sigmoid form keeps its relative
+// accuracy in the negative tail, where 0.5 x (1 + tanh u) written as 1 - 2 rcp(exp(2u) + 1) cancels (from x = -4 down)
 
 template <bool ERF>
 __global__ __launch_bounds__(256) void gelu_fwd_kernel(const __bf16* __restrict__ pre, long ldp, __bf16* __restrict__ out,
@@ -972,7 +983,7 @@ __global__ __launch_bounds__(256) void gelu_fwd_kernel(const __bf16* __restrict_
     const bf16x8 x = *(const bf16x8*)(pre + m * ldp + c);
     bf16x8 o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = f2bf(ERF ? gelu_erf_f(bf2f(x[e])) : gelu_new_fast(bf2f(x[e])));
+    for (int e = 0; e < 8; ++e) o[e] = f2bf(ERF ? gelu_erf_f(bf2f(x[e])) : gelu_new_f(bf2f(x[e])));
     *(bf16x8*)(out + m * ldo + c) = o;
   }
 }
@@ -984,7 +995,7 @@ __global__ void gelu_fwd_scalar_kernel(const __bf16* __restrict__ pre, long ldp,
   for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int m = (int)(i / N), n = (int)(i % N);
     const float x = bf2f(pre[m * ldp + n]);
-    out[m * ldo + n] = f2bf(ERF ? gelu_erf_f(x) : gelu_new_fast(x));
+    out[m * ldo + n] = f2bf(ERF ? gelu_erf_f(x) : gelu_new_f(x));
   }
 }
 

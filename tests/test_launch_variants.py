@@ -1,13 +1,16 @@
 """Kernels that only a launch-time environment variable selects (read once per process, so each needs a fresh one):
 ``IIT_LN_PART_R`` = 2 / 4 (``ln_bwd_part_kernel<*, *, 2 / 4>``), ``IIT_ADAM_NT`` = 0 (``adam_span_kernel<false,
-4>``) and ``IIT_ADAM_UNROLL`` = 1 / 2 (``adam_span_kernel<true, 1 / 2>``).  Three child processes, one at a time, each
-with one layer-norm and / or one Adam variable set, run the fused layer-norm backward and row-select cases of
-tests/test_ln_exact.py and the single-step cases of tests/test_adam_exact.py under their own time limit; the loop
+4>``), ``IIT_ADAM_UNROLL`` = 1 / 2 (``adam_span_kernel<true, 1 / 2>``) and ``IIT_EMBED_BWD_POS`` = 0 (the token-major
+``embed_bwd_kernel``).  Three child processes, one at a time, each with one layer-norm and / or one Adam variable set
+(the third the embedding variable too), run the fused layer-norm backward and row-select cases of
+tests/test_ln_exact.py, the single-step cases of tests/test_adam_exact.py and, in the third, the embedding backward
+cases of tests/test_embed_exact.py under their own time limit; the loop
 ends at the first child that does not exit with 0, so nothing more starts on the GPU after a fault, an abort or a
 timeout.  ``adam_span_kernel<false, 1 / 2>`` (both variables at once) is run by no test.
 
-Measured on an MI355X: one case, passed, none skipped, 22.3 s -- three children of about 7 s each, most of it the
-start of a fresh process (interpreter, torch, the first launch); the children select 164, 164 and 26 cases.
+Measured on an MI355X: one case, passed, none skipped, 23.0 s -- three children of about 7 s each, most of it the
+start of a fresh process (interpreter, torch, the first launch); the children select 164, 164 and 94 cases (26 Adam
+and 68 embedding backward cases in the third).
 """
 import os
 import subprocess
@@ -20,17 +23,18 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 LN = "(test_ln_bwd and not xh16) or row_select"
 ADAM = "test_adam_step or guard or non_finite"
-VARIANTS = [({"IIT_LN_PART_R": "2", "IIT_ADAM_NT": "0"}, f"({LN}) or {ADAM}"),
-            ({"IIT_LN_PART_R": "4", "IIT_ADAM_UNROLL": "1"}, f"({LN}) or {ADAM}"),
-            ({"IIT_ADAM_UNROLL": "2"}, ADAM)]
+EMBED = "test_embed_bwd"
+FILES = ["test_ln_exact.py", "test_adam_exact.py"]
+VARIANTS = [({"IIT_LN_PART_R": "2", "IIT_ADAM_NT": "0"}, FILES, f"({LN}) or {ADAM}"),
+            ({"IIT_LN_PART_R": "4", "IIT_ADAM_UNROLL": "1"}, FILES, f"({LN}) or {ADAM}"),
+            ({"IIT_ADAM_UNROLL": "2", "IIT_EMBED_BWD_POS": "0"}, FILES + ["test_embed_exact.py"], f"{ADAM} or {EMBED}")]
 LIMIT_S = 240
 
 
 def test_launch_time_variants():
-    for env, expr in VARIANTS:
+    for env, files, expr in VARIANTS:
         cmd = ["timeout", "-k", "10", str(LIMIT_S), sys.executable, "-m", "pytest", "-q", "-x", "-p",
-               "no:cacheprovider", os.path.join(HERE, "test_ln_exact.py"), os.path.join(HERE, "test_adam_exact.py"),
-               "-k", expr]
+               "no:cacheprovider"] + [os.path.join(HERE, f) for f in files] + ["-k", expr]
         res = subprocess.run(cmd, env=dict(os.environ, **env), cwd=os.path.dirname(HERE), stdout=subprocess.PIPE,
                              stderr=subprocess.STDOUT, text=True)
         tail = "\n".join(res.stdout.splitlines()[-25:])
