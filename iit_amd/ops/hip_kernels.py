@@ -1005,6 +1005,17 @@ def rms_bwd(dy, x, rstd, w, dx, dw, T: int, d: int, dres=None):
 def rotary(x, out, cos, sin, rd: int, offset: int, adjacent: bool, inverse: bool):
     """out [B,S,H,D] contiguous = rotary(x) (x any batch/position/head strides, unit d stride), bf16."""
     B, S, H, D = x.shape
+    if x.dtype != torch.bfloat16 or x.stride(-1) != 1:
+        raise ValueError(f"rotary: x must be bf16 with unit stride on its last dimension, got {x.dtype}, "
+                         f"stride {x.stride()}")
+    for name, t in (("cos", cos), ("sin", sin)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"rotary: {name} must be contiguous fp32, got {t.dtype}, stride {t.stride()}")
+        if t.dim() != 2 or t.shape[1] != rd:
+            raise ValueError(f"rotary: {name} must be [n_ctx, {rd}], got {tuple(t.shape)}")
+        if t.shape[0] < offset + S:
+            raise ValueError(f"rotary: {name} has {t.shape[0]} rows, positions {offset} .. {offset + S - 1} need "
+                             f"{offset + S}")
     _check(lib().iit_rotary(_p(x), x.stride(0), x.stride(1), x.stride(2), _p(out), _p(cos), _p(sin), int(inverse),
                             B, S, H, D, rd, offset, int(adjacent), _stream()), "rotary")
 
