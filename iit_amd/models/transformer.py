@@ -274,7 +274,11 @@ class Attention(nn.Module):
                 z = ops.attention(q, k, v, causal, self.attn_scale, patch_heads=heads, patch_src=z_spl[0].src)
                 return z, True
             return ops.attention(q, k, v, causal, self.attn_scale), False
-        z = TorchOps.attention(
+        native = getattr(ops, "native_attention", False)  # hip32x: an unfused backend with an attention kernel
+        if native and not (run.live(self.hook_attn_scores) or run.live(self.hook_pattern)) \
+                and self.ignore_value() == float("-inf"):
+            return ops.attention(q, k, v, causal, self.attn_scale), False
+        z = (type(ops) if native else TorchOps).attention(  # a native backend counts the call as its fallback
             ops, q, k, v, causal, self.attn_scale,
             hook_scores=lambda t: run.site(self.hook_attn_scores, t),
             hook_pattern=lambda t: run.site(self.hook_pattern, t),

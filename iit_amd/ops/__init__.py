@@ -6,6 +6,9 @@
 * ``hip32`` – :class:`iit_amd.ops.hip32_ops.HipF32Ops`, ``TorchOps`` in fp32 with the
   projections on the exact-fp32 MFMA GEMM (``csrc/gemm_f32.hip``).  Opt-in only:
   ``backend=None`` never selects it; on a CPU model or without the extension it raises.
+* ``hip32x`` – :class:`iit_amd.ops.hip32_ops.HipF32XOps`, ``hip32`` with attention on the
+  exact-fp32 MFMA kernel (``csrc/attn_fp32.hip``, S <= 64 and d_head <= 64; the torch op
+  otherwise and whenever a score / pattern hook is live).  Opt-in under ``hip32``'s rules.
 
 ``select_ops(model, backend)`` picks per call: ``backend=None`` means "hip when
 the model lives on a GPU and computes in bf16, else torch".  Asking for ``hip``
@@ -53,11 +56,11 @@ def select_ops(model, backend: Optional[str] = None):
             raise RuntimeError("hip op backend requires the model on a GPU")
         from .hip_ops import get_hip_ops
         return get_hip_ops(model)
-    if backend == "hip32":  # opt-in only: ``backend=None`` never selects it
+    if backend in ("hip32", "hip32x"):  # opt-in only: ``backend=None`` never selects them
         if not on_gpu:
-            raise RuntimeError("hip32 op backend requires the model on a GPU")
-        from .hip32_ops import get_hip32_ops
-        return get_hip32_ops(model)
+            raise RuntimeError(f"{backend} op backend requires the model on a GPU")
+        from .hip32_ops import get_hip32_ops, get_hip32x_ops
+        return (get_hip32_ops if backend == "hip32" else get_hip32x_ops)(model)
     raise ValueError(f"unknown op backend {backend}")
 
 

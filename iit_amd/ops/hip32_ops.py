@@ -6,6 +6,9 @@
 stay where the fp32 torch path has them.  Gradients are returned to autograd exactly as ``x @ W`` returns them
 (no direct arena accumulation).  The backend is never chosen automatically: ``select_ops(model, "hip32")`` or
 ``model.set_op_backend("hip32")``.
+
+``hip32x`` (:class:`HipF32XOps`) is ``hip32`` plus attention on the exact-fp32 MFMA kernel of
+``csrc/attn_fp32.hip`` (:class:`AttentionF32Fn`), opt-in in the same way.
 """
 from __future__ import annotations
 
@@ -251,15 +254,72 @@ class HipF32Ops(TorchOps):
         return self._lin("unembed", x, W_U, b_U)
 
 
-_OPS = None
+def _unit_last(t: torch.Tensor) -> torch.Tensor:
+    return t if t.stride(-1) == 1 or t.shape[-1] == 1 else t.contiguous()
+
+
+class AttentionF32Fn(torch.autograd.Function):
+    """``z = softmax(scale q k^T (causal mask)) v`` for fp32 q, k, v ``[B][S][H][dh]`` on ``csrc/attn_fp32.hip``
+    (``S <= 64``, ``dh <= 64``).  The operands are taken as stored (the q / k / v views of ``QKVF32Fn``'s packed
+    output are the normal case); only one whose last stride is not 1 is copied.  q, k, v and the row log-sum-exp are
+    saved; the backward is one launch that recomputes P and writes dq, dk, dv."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, causal: bool, scale: float):
+        q, k, v = (_unit_last(t.detach()) for t in (q, k, v))
+        B, S, H, dh = q.shape
+        z = torch.empty(B, S, H, dh, dtype=torch.float32, device=q.device)
+        lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
+        K.attn_f32_fwd(q, k, v, z, lse, scale, causal)
+        ctx.save_for_backward(q, k, v, lse)
+        ctx.causal, ctx.scale = bool(causal), float(scale)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        q, k, v, lse = ctx.saved_tensors
+        dq, dk, dv = (torch.empty(q.shape, dtype=torch.float32, device=q.device) for _ in range(3))
+        K.attn_f32_bwd(q, k, v, _unit_last(dz), lse, dq, dk, dv, ctx.scale, ctx.causal)
+        need = ctx.needs_input_grad
+        return dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None
+
+
+class HipF32XOps(HipF32Ops):
+    """:class:`HipF32Ops` with attention on ``csrc/attn_fp32.hip`` as well.  ``calls`` (its own dictionary, not
+    ``HipF32Ops.calls``) also counts ``"attention"`` (the kernel ran) and ``"attention_fallback"`` (the inherited
+    torch op: S or dh above 64, a non-fp32 or CPU operand, or the hooks / masked fill that ``compute_z`` passes on
+    when a score or pattern hook is live or the fill is not ``-inf``).  ``native_attention`` tells
+    ``Attention.compute_z`` to call ``attention`` instead of ``TorchOps.attention``."""
+    name = "hip32x"
+    fused = False
+    native_attention = True
+    calls: dict = {}
+
+    def attention(self, q, k, v, causal: bool, attn_scale: float, **kw):
+        if not kw and K.attn_f32_ok(q, k, v):
+            self._count("attention")
+            return AttentionF32Fn.apply(q, k, v, causal, 1.0 / attn_scale)
+        self._count("attention_fallback")
+        return TorchOps.attention(self, q, k, v, causal, attn_scale, **kw)
+
+
+_OPS = {}
+
+
+def _get(cls, model):
+    if model.cfg.dtype != torch.float32:
+        raise RuntimeError(f"{cls.name} op backend computes in fp32; the model's dtype is {model.cfg.dtype}")
+    K.lib()
+    if cls not in _OPS:
+        _OPS[cls] = cls()
+    return _OPS[cls]
 
 
 def get_hip32_ops(model) -> HipF32Ops:
     """The backend for an fp32 model on a GPU; raises when the kernel library cannot be loaded (no fallback)."""
-    global _OPS
-    if model.cfg.dtype != torch.float32:
-        raise RuntimeError(f"hip32 op backend computes in fp32; the model's dtype is {model.cfg.dtype}")
-    K.lib()
-    if _OPS is None:
-        _OPS = HipF32Ops()
-    return _OPS
+    return _get(HipF32Ops, model)
+
+
+def get_hip32x_ops(model) -> HipF32XOps:
+    """``hip32x`` under the same rules as :func:`get_hip32_ops`."""
+    return _get(HipF32XOps, model)

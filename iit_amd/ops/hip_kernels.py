@@ -34,6 +34,11 @@ _SIGS = {
     "iit_gemm": [c_void_p] * 10 + [c_long] * 5 + [c_int] * 12 + [c_void_p],
     "iit_gemm_f32": [c_void_p] * 6 + [c_long] * 4 + [c_int] * 7 + [c_void_p],
     "iit_gemm_f32_ok": [c_void_p] * 6 + [c_long] * 4 + [c_int] * 7,
+    "iit_attn_f32_lds": [c_int] * 3,
+    "iit_attn_f32_waves": [c_int] * 3,
+    "iit_attn_f32_ok": [c_void_p] * 4 + [c_int] * 4,
+    "iit_attn_f32_fwd": [c_void_p] * 6 + [c_int] * 4 + [c_float, c_int, c_void_p],
+    "iit_attn_f32_bwd": [c_void_p] * 9 + [c_int] * 4 + [c_float, c_int, c_void_p],
     "iit_gemm_glds": [c_void_p] * 8 + [c_long] * 5 + [c_int] * 8 + [c_void_p] * 4,
     "iit_gemm_glds_ok": [c_void_p] * 5 + [c_long] * 5 + [c_int] * 9,
     "iit_gemm_glds_sm": [c_void_p] * 8 + [c_long] * 5 + [c_int] * 8 + [c_void_p] * 3 + [c_int] + [c_void_p] * 3,
@@ -426,6 +431,87 @@ def gemm_f32(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, bias=None, resid=Non
     ws = torch.empty(splits * M * N, dtype=torch.float32, device=A.device) if splits > 1 else None
     _check(lib().iit_gemm_f32(_p(A), _p(B), _p(C), _p(bias), _p(resid), _p(ws), lda, ldb, ldc, ldr, M, N, K, mode, epi,
                               tile, splits, _stream()), "iit_gemm_f32")
+
+
+# ------------------------------------------------------------------------------ fp32 attention (csrc/attn_fp32.hip)
+ATTN_F32_LDS_MAX = 160 * 1024  # one CU's LDS: what a workgroup of the fp32 attention kernels can get
+ATTN_F32_MAX_S = ATTN_F32_MAX_DH = 64
+
+
+def attn_f32_lds(S: int, dh: int, backward: bool) -> int:
+    """Bytes of dynamic LDS one workgroup of ``iit_attn_f32_fwd`` / ``iit_attn_f32_bwd`` asks for: per wave (one
+    (batch, head)) three / four ``[Sp][Dp + 2]`` operand images and one / two ``[Sp][Sp + 2]`` score tables (the
+    forward adds a row of Sp sums), Sp and Dp = S and dh rounded up to 16, times ``attn_f32_waves``."""
+    return int(lib().iit_attn_f32_lds(S, dh, int(backward))) * attn_f32_waves(S, dh, backward)
+
+
+def attn_f32_waves(S: int, dh: int, backward: bool) -> int:
+    """Waves per workgroup of the fp32 attention kernels: as many as fit ``ATTN_F32_LDS_MAX``, at most 4."""
+    return int(lib().iit_attn_f32_waves(S, dh, int(backward)))
+
+
+def _attn_f32_why(ts: dict) -> Optional[str]:
+    """Why the fp32 attention kernels do not take the named ``[B][S][H][dh]`` tensors (None when they do)."""
+    shape = None
+    for name, t in ts.items():
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            return f"{name} must be a [B][S][H][dh] tensor"
+        if not t.is_cuda or t.dtype != torch.float32:
+            return f"{name} must be fp32 on the GPU, got {t.dtype} on {t.device}"
+        shape = shape or tuple(t.shape)
+        if tuple(t.shape) != shape:
+            return f"{name} has shape {tuple(t.shape)}, expected {shape}"
+        if t.shape[3] > 1 and t.stride(3) != 1:
+            return f"{name} must have unit stride on its last dimension, got stride {t.stride()}"
+    B, S, H, dh = shape
+    if min(shape) < 1 or S > ATTN_F32_MAX_S or dh > ATTN_F32_MAX_DH:
+        return f"shape {shape} outside 1 <= S <= {ATTN_F32_MAX_S}, 1 <= dh <= {ATTN_F32_MAX_DH}"
+    ptrs = [_p(t) for t in ts.values()][:4]
+    ptrs += ptrs[:1] * (4 - len(ptrs))  # the predicate takes four operands; q, k, v alone: q stands in
+    if not lib().iit_attn_f32_ok(*ptrs, B, S, H, dh):
+        return f"iit_attn_f32_ok refuses shape {shape}"
+    return None
+
+
+def attn_f32_ok(q, k, v) -> bool:
+    """Whether ``csrc/attn_fp32.hip`` takes q, k, v: fp32 GPU ``[B][S][H][dh]`` tensors of one shape with unit last
+    stride (any batch / position / head strides, any 4-byte aligned base), ``S <= 64`` and ``dh <= 64``."""
+    return _attn_f32_why({"q": q, "k": k, "v": v}) is None
+
+
+def _strides3(*ts):
+    vals = [s for t in ts for s in t.stride()[:3]]
+    return (c_long * len(vals))(*vals)
+
+
+def _attn_f32_check(what: str, ts: dict, lse):
+    why = _attn_f32_why(ts)
+    if why is None:
+        B, S, H, _ = next(iter(ts.values())).shape
+        if not (lse.is_cuda and lse.dtype == torch.float32 and tuple(lse.shape) == (B, H, S) and lse.is_contiguous()):
+            why = f"lse must be contiguous fp32 [B][H][S] on the GPU, got {lse.dtype} {tuple(lse.shape)}"
+    if why is not None:
+        raise ValueError(f"{what}: {why}")
+
+
+def attn_f32_fwd(q, k, v, z, lse, scale: float, causal: bool):
+    """``z = softmax(scale q k^T (causal mask)) v`` and ``lse`` (natural log) in exact fp32 on the MFMA units
+    (``csrc/attn_fp32.hip``); q, k, v, z ``[B][S][H][dh]`` with their own strides, lse ``[B][H][S]``.  Launches on
+    the current stream; raises ``ValueError``, without launching, for what ``attn_f32_ok`` refuses."""
+    _attn_f32_check("attn_f32_fwd", {"q": q, "k": k, "v": v, "z": z}, lse)
+    B, S, H, dh = q.shape
+    _check(lib().iit_attn_f32_fwd(_p(q), _p(k), _p(v), _p(z), _p(lse), _strides3(q, k, v, z), B, S, H, dh, scale,
+                                  int(causal), _stream()), "iit_attn_f32_fwd")
+
+
+def attn_f32_bwd(q, k, v, do, lse, dq, dk, dv, scale: float, causal: bool):
+    """dq, dk, dv of :func:`attn_f32_fwd` from dO and the stored lse (P is recomputed, D = rowsum(P o dP)); same
+    layout rules and refusals."""
+    _attn_f32_check("attn_f32_bwd", {"q": q, "k": k, "v": v, "do": do, "dq": dq, "dk": dk, "dv": dv}, lse)
+    B, S, H, dh = q.shape
+    _check(lib().iit_attn_f32_bwd(_p(q), _p(k), _p(v), _p(do), _p(lse), _p(dq), _p(dk), _p(dv),
+                                  _strides3(q, k, v, do, dq, dk, dv), B, S, H, dh, scale, int(causal), _stream()),
+           "iit_attn_f32_bwd")
 
 
 # ------------------------------------------------------------------------------ dual GEMM (csrc/gemm_dual.hip)

@@ -1,14 +1,15 @@
 """Per-call timing of fp32 attention, forward + backward, at the shapes of the fp32 models: what the op costs today on
 the fp32 torch path (``TorchOps.attention`` under autograd: two batched einsums with their permute copies, a divide,
 a masked fill, softmax, the NaN scrub and a ``where``, and autograd's backward of each), the number an fp32 attention
-kernel has to beat.  ``CANDIDATES`` is the list of implementations; a kernel joins it with one entry.
+kernel has to beat.  ``CANDIDATES`` is the list of implementations; ``GPU_CANDIDATES`` adds the fp32 MFMA kernel of
+csrc/attn_fp32.hip (``AttentionF32Fn``) when the device is a GPU.
 
 Each candidate's forward + backward is captured as a graph of ``--inner`` back-to-back calls; the graphs are replayed
 alternately for ``--rounds`` rounds on one device and timed with device events.  The table gives the median and the
 minimum microseconds per call, the ratio to the first candidate, and that time times the layers of the 6L model.
 Without a GPU (``--device cpu``, tests) the calls run eagerly under a wall clock.
 
-    python scripts/bench_attn_f32.py --out profiles/attn_f32_torch_6l.txt
+    python scripts/bench_attn_f32.py --out profiles/attn_f32_kernel_6l.txt
 """
 from __future__ import annotations
 
@@ -35,7 +36,19 @@ def torch_attention(q, k, v, causal: bool, scale: float):
     return TorchOps.attention(None, q, k, v, causal, 1.0 / scale)  # the op reads nothing from its backend object
 
 
-CANDIDATES = {"torch": torch_attention}
+def hip32x_attention(q, k, v, causal: bool, scale: float):
+    """``AttentionF32Fn``: the fp32 MFMA kernels of csrc/attn_fp32.hip, as the ``hip32x`` backend calls them."""
+    from iit_amd.ops.hip32_ops import AttentionF32Fn
+    return AttentionF32Fn.apply(q, k, v, causal, scale)
+
+
+CANDIDATES = {"torch": torch_attention}  # what runs on any device
+GPU_CANDIDATES = {"hip32x": hip32x_attention}
+
+
+def candidates(device) -> dict:
+    """``CANDIDATES``, on a GPU followed by the kernels that need one."""
+    return {**CANDIDATES, **GPU_CANDIDATES} if torch.device(device).type == "cuda" else dict(CANDIDATES)
 
 
 def operands(B, S, H, dh, device, seed: int = 0):
@@ -126,7 +139,7 @@ def main(argv=None):
     args = parse(argv)
     if args.device == "cuda" and not torch.cuda.is_available():
         raise SystemExit("bench_attn_f32.py measures on a GPU; none is visible (--device cpu runs it eagerly)")
-    text = "\n".join(table(args.device, args.inner, args.rounds)) + "\n"
+    text = "\n".join(table(args.device, args.inner, args.rounds, fns=candidates(args.device))) + "\n"
     print(text)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
