@@ -11,6 +11,7 @@
 // the dW tiles (split-major, so the K-splits of a tile are a launch round apart and its reduction ticket is taken
 // late), the rest the dX tiles.  The dW problem comes first because its K (the token count) is the longer loop.
 #include "gemm_glds_body.h"
+#include "prefetch.h"
 
 namespace {
 
@@ -26,36 +27,8 @@ struct Cfg {
 // back because its forward-saved activation and its weight come from HBM, not the Infinity Cache): the first
 // ``pf.wgs`` workgroups of the launch read the NEXT pair's cold operands (up to two ranges) once, one 4-B load per
 // 64-B granule, so they are cache-resident when that pair starts.  They run beside the tiles, whose operand intake is
-// L2 -> LDS bound and leaves HBM bandwidth unused.  Loads only: nothing is written.
-struct Prefetch {
-  const char* p[2];
-  long bytes[2];
-  int wgs;
-};
-
-__device__ __forceinline__ void prefetch_part(const Prefetch& pf, int part) {
-  unsigned acc = 0u;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    if (!pf.p[r] || pf.bytes[r] <= 0) continue;
-    const long gran = (pf.bytes[r] + 63) / 64;
-    const long per = (gran + pf.wgs - 1) / pf.wgs;
-    const long g0 = (long)part * per;
-    const long g1 = g0 + per < gran ? g0 + per : gran;
-    const char* base = pf.p[r];
-    for (long g = g0 + threadIdx.x; g < g1; g += (long)blockDim.x * 8) {
-      unsigned v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const long gg = g + (long)u * blockDim.x;
-        v[u] = gg < g1 ? *(const unsigned*)(base + gg * 64) : 0u;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc ^= v[u];
-    }
-  }
-  asm volatile("" ::"v"(acc));  // keep the loads
-}
+// L2 -> LDS bound and leaves HBM bandwidth unused.  Loads only: nothing is written.  (Prefetch / prefetch_part:
+// csrc/prefetch.h)
 
 template <class TW, int EW, class TX, int EX>
 __global__ __launch_bounds__(TW::NW * 64, TW::OCC) void gemm_dual_kernel(G2Args pw, G2Args px, int w_tiles,

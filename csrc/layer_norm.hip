@@ -9,6 +9,7 @@
 // 8-B bf16 accesses; needs d % 4 == 0 and aligned rows, ln_vec), W = 1 covers any d <= 4096 and any alignment.
 // The row arithmetic is written once over Pack<W> and shared by both widths.
 #include "common.h"
+#include "prefetch.h"
 #include <initializer_list>
 #include <stdlib.h>
 #include <type_traits>
@@ -103,14 +104,22 @@ __device__ __forceinline__ bool sel_hit(const RowSel& sel, int row) {
 
 // ============================================================================ forward
 // ``y32`` (nullable, W = 4 only): the fp32 twin of the rounded output (a post-norm block's residual operand: no
-// separate cast pass)
+// separate cast pass).
+// ``pf``: the first pf.wgs workgroups of the grid do no row work: they read the weights of the GEMMs that follow this
+// norm (the block's bf16 mirrors, HBM-cold after the optimizer pass) into the caches and leave (csrc/prefetch.h); at
+// the front of the grid, so their HBM latency runs under the row work.  The row blocks follow them.
 template <int W, int N>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                      const float* __restrict__ b, __bf16* __restrict__ y,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                     int T, int d, float eps, RowSel sel, float* __restrict__ y32) {
+                                                     int T, int d, float eps, RowSel sel, float* __restrict__ y32,
+                                                     Prefetch pf) {
   using P = Pack<W>;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if ((int)blockIdx.x < pf.wgs) {  // uniform over the block
+    prefetch_part(pf, blockIdx.x);
+    return;
+  }
+  const int row = (blockIdx.x - pf.wgs) * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= T) return;
   const int dn = d / W;
@@ -483,19 +492,32 @@ static void ln_flag(bool b, F&& f) {
 }
 
 // ``y32`` (nullable): also writes fp32(y); vector layout only, refused (nothing launched) elsewhere.  ``pos_mask``
-// (RowSel): base rows [0, Tb) at positions with their bit set normalise the source row row + Tb
-IIT_EXPORT int iit_ln_fwd(const float* x, const float* w, const float* b, void* y, float* y32, float* mean,
-                          float* rstd, int T, int d, float eps, unsigned long long pos_mask, int S, int Tb,
-                          void* stream) {
+// (RowSel): base rows [0, Tb) at positions with their bit set normalise the source row row + Tb.
+// ``pf0`` / ``pf1`` (nullable, ``pf*_bytes`` long; whole 4-B words are read) are read into the caches by ``pf_wgs``
+// (<= 1024) extra workgroups in front of the row blocks: the weights of the GEMMs that follow.  Without a range or
+// with pf_wgs <= 0 the grid is the row blocks alone.
+IIT_EXPORT int iit_ln_fwd_pf(const float* x, const float* w, const float* b, void* y, float* y32, float* mean,
+                             float* rstd, int T, int d, float eps, unsigned long long pos_mask, int S, int Tb,
+                             const void* pf0, long pf0_bytes, const void* pf1, long pf1_bytes, int pf_wgs,
+                             void* stream) {
   if (pos_mask && (S <= 0 || S > 64 || 2 * (long)Tb > T)) return (int)hipErrorInvalidValue;
   const bool vec = ln_vec(d, {f32_rows(x), bf16_rows(y), f32_rows(y32), f32_rows(w), f32_rows(b)});
   if (d > 4096 || (y32 && !vec)) return (int)hipErrorInvalidValue;
   const RowSel sel{pos_mask, S > 0 ? S : 1, Tb};
+  Prefetch pf{{(const char*)pf0, (const char*)pf1}, {pf0 ? pf0_bytes & ~3L : 0, pf1 ? pf1_bytes & ~3L : 0}, 0};
+  if (((uintptr_t)pf0 | (uintptr_t)pf1) & 3) return (int)hipErrorInvalidValue;
+  if ((pf.bytes[0] > 0 || pf.bytes[1] > 0) && pf_wgs > 0) pf.wgs = pf_wgs < 1024 ? pf_wgs : 1024;
   ln_dispatch(vec, d, [&](auto W, auto N) {
-    hipLaunchKernelGGL((ln_fwd_kernel<W, N>), dim3((T + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, w, b,
-                       (__bf16*)y, mean, rstd, T, d, eps, sel, y32);
+    hipLaunchKernelGGL((ln_fwd_kernel<W, N>), dim3(pf.wgs + (T + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, w, b,
+                       (__bf16*)y, mean, rstd, T, d, eps, sel, y32, pf);
   });
   return hipGetLastError();
+}
+
+IIT_EXPORT int iit_ln_fwd(const float* x, const float* w, const float* b, void* y, float* y32, float* mean,
+                          float* rstd, int T, int d, float eps, unsigned long long pos_mask, int S, int Tb,
+                          void* stream) {
+  return iit_ln_fwd_pf(x, w, b, y, y32, mean, rstd, T, d, eps, pos_mask, S, Tb, nullptr, 0, nullptr, 0, 0, stream);
 }
 
 // rows per block of the fused affine-gradient backward (the caller sizes ``part`` as blocks x 2 d floats)

@@ -135,9 +135,10 @@ class LayerNormSite(nn.Module):
             raise NotImplementedError(f"normalization_type {kind}")
         return LayerNormSite(cfg, affine=kind in ("LN", "RMS"), rms=kind in ("RMS", "RMSPre"))
 
-    def run(self, x, run: _Run, twin: bool = False):
+    def run(self, x, run: _Run, twin: bool = False, prefetch=None):
         """``twin``: the output will also be a residual operand (post-norm blocks): the fused backend then returns
-        it with an fp32 twin (``HipOps.layer_norm_twin``)."""
+        it with an fp32 twin (``HipOps.layer_norm_twin``).  ``prefetch``: ``HipOps.fwd_prefetch`` of the weights that
+        follow this norm (None on every other backend)."""
         live = run.live(self.hook_scale) or run.live(self.hook_normalized)
         if self.rms:
             hs = (lambda t: run.site(self.hook_scale, t)) if live else None
@@ -149,9 +150,10 @@ class LayerNormSite(nn.Module):
                 hook_scale=lambda t: run.site(self.hook_scale, t),
                 hook_normalized=lambda t: run.site(self.hook_normalized, t),
             )
+        kw = {} if prefetch is None else {"prefetch": prefetch}
         if twin and self.w is not None and hasattr(run.ops, "layer_norm_twin"):
-            return run.ops.layer_norm_twin(x, self.w, self.b, self.eps)
-        return run.ops.layer_norm(x, self.w, self.b, self.eps)
+            return run.ops.layer_norm_twin(x, self.w, self.b, self.eps, **kw)
+        return run.ops.layer_norm(x, self.w, self.b, self.eps, **kw)
 
 
 def rotary_tables(cfg: HookedTransformerConfig):
@@ -339,16 +341,23 @@ class TransformerBlock(nn.Module):
             self.hook_resid_mid = HookPoint()
         self.hook_resid_post = HookPoint()
 
-    def _norm(self, ln, x, run):
+    @staticmethod
+    def _fwd_prefetch(ops, *Ws):
+        """The weights of the GEMMs after a norm, as the fused backend wants them for the norm's ``prefetch=``
+        (``HipOps.fwd_prefetch``: its LN launch reads them into the caches); None on every other backend."""
+        f = getattr(ops, "fwd_prefetch", None)
+        return f(*Ws) if f is not None else None
+
+    def _norm(self, ln, x, run, prefetch=None):
         if ln is None:
             return x.to(run.ops.dtype)
-        return ln.run(x, run)
+        return ln.run(x, run, prefetch=prefetch)
 
-    def _norm_fork(self, ln, x, run):
+    def _norm_fork(self, ln, x, run, prefetch=None):
         """(normed x, residual to carry forward): fused backends return a passthrough of ``x`` whose
         gradient the LN (or RMSNorm) backward kernel adds in (one pass instead of norm-bwd + autograd's sum)."""
         if ln is None or run.live(ln.hook_scale) or run.live(ln.hook_normalized) or not x.requires_grad:
-            return self._norm(ln, x, run), x
+            return self._norm(ln, x, run, prefetch), x
         if ln.rms:
             fork = getattr(run.ops, "rms_norm_fork", None)
             out = fork(x, ln.w, ln.eps) if fork is not None else None
@@ -356,7 +365,7 @@ class TransformerBlock(nn.Module):
         fork = getattr(run.ops, "layer_norm_fork", None)
         if fork is None:
             return self._norm(ln, x, run), x
-        return fork(x, ln.w, ln.b, ln.eps)
+        return fork(x, ln.w, ln.b, ln.eps, **({} if prefetch is None else {"prefetch": prefetch}))
 
     def last_position_ok(self, run: _Run) -> bool:
         """Whether this (final) block may compute only the last position after attention: nothing observes
@@ -386,7 +395,7 @@ class TransformerBlock(nn.Module):
         if spl is not None and not attn.inner_live(run) and not ln1_live:
             z = run.site(attn.hook_z, spl.src.to(ops.dtype), spliced=True)
         else:
-            x, resid = self._norm_fork(self.ln1, resid, run)
+            x, resid = self._norm_fork(self.ln1, resid, run, self._fwd_prefetch(ops, attn.W_Q, attn.W_O))
             z, spliced = attn.compute_z(x, run)
             z = run.site(attn.hook_z, z, spliced=spliced)
         if last_only:
@@ -418,11 +427,11 @@ class TransformerBlock(nn.Module):
               and self.cfg.act_fn in ("gelu_new", "gelu_fast", "gelu_pytorch_tanh")
               and not (ln2_live or run.live(mlp.hook_pre) or run.live(mlp.hook_post) or run.live(self.hook_mlp_out))):
             # no MLP site observed: one fused op whose backward forms dpre in the dX GEMM epilogue
-            x, resid_mid = self._norm_fork(self.ln2, resid_mid, run)
+            x, resid_mid = self._norm_fork(self.ln2, resid_mid, run, self._fwd_prefetch(ops, mlp.W_in, mlp.W_out))
             resid_post = ops.mlp_gelu_residual(x, mlp.W_in, mlp.b_in, mlp.W_out, mlp.b_out, resid_mid)
             return run.site(self.hook_resid_post, resid_post)
         else:
-            x, resid_mid = self._norm_fork(self.ln2, resid_mid, run)
+            x, resid_mid = self._norm_fork(self.ln2, resid_mid, run, self._fwd_prefetch(ops, mlp.W_in, mlp.W_out))
             pre_hook = (lambda t: run.site(mlp.hook_pre, t)) if run.live(mlp.hook_pre) else None
             spliced = False
             if mlp.gated:
@@ -472,10 +481,11 @@ class TransformerBlock(nn.Module):
         causal = self.cfg.attention_dir == "causal"
         S, H, dh = p.full.shape[1], self.cfg.n_heads, self.cfg.d_head
         mirror = ops.pair_heads_ok(S, dh) and H <= 64
+        pf1 = ops.fwd_prefetch(attn.W_Q, attn.W_O)
         if zs is not None and any(ix.is_everything() for ix in zs):
             # the base z is the source z: the base attention is dead, compute the source rows only
             with torch.no_grad():
-                x = ops.layer_norm(p.src, self.ln1.w, self.ln1.b, self.ln1.eps)
+                x = ops.layer_norm(p.src, self.ln1.w, self.ln1.b, self.ln1.eps, prefetch=pf1)
                 q, k, v = ops.qkv(x, attn.W_Q, attn.W_K, attn.W_V, attn.b_Q, attn.b_K, attn.b_V)
                 if mirror:  # stored into both halves by the attention kernel itself
                     zf = ops.attention_dual(q, causal, attn.attn_scale)
@@ -485,7 +495,7 @@ class TransformerBlock(nn.Module):
             z = _hip_ops().Paired(zf[:p.nb], zf)
             resid = p
         else:
-            x, resid = ops.pair_layer_norm_fork(p, self.ln1.w, self.ln1.b, self.ln1.eps)
+            x, resid = ops.pair_layer_norm_fork(p, self.ln1.w, self.ln1.b, self.ln1.eps, prefetch=pf1)
             qkv = ops.pair_qkv(x, attn.W_Q, attn.W_K, attn.W_V, attn.b_Q, attn.b_K, attn.b_V)
             heads, rest = None, list(zs or ())
             z = None
@@ -512,18 +522,19 @@ class TransformerBlock(nn.Module):
         pname = mlp.hook_post.name
         ps = sites.get(pname)
         erf = False  # gelu_new family only (paired_ok)
+        pf2 = ops.fwd_prefetch(mlp.W_in, mlp.W_out)
         if ps is None:
-            x, resid2 = ops.pair_layer_norm_fork(resid_mid, self.ln2.w, self.ln2.b, self.ln2.eps)
+            x, resid2 = ops.pair_layer_norm_fork(resid_mid, self.ln2.w, self.ln2.b, self.ln2.eps, prefetch=pf2)
             return ops.pair_mlp_gelu_residual(x, mlp.W_in, mlp.b_in, mlp.W_out, mlp.b_out, resid2, erf=erf), True
         if any(ix.is_everything() for ix in ps):
             with torch.no_grad():
-                x = ops.layer_norm(resid_mid.src, self.ln2.w, self.ln2.b, self.ln2.eps)
+                x = ops.layer_norm(resid_mid.src, self.ln2.w, self.ln2.b, self.ln2.eps, prefetch=pf2)
                 _, post_src = ops.mlp_in(x, mlp.W_in, mlp.b_in, self.cfg.act_fn)
             qf = torch.cat([post_src, post_src])
             post = _hip_ops().Paired(qf[:post_src.shape[0]], qf)
             resid2 = resid_mid
         else:
-            x, resid2 = ops.pair_layer_norm_fork(resid_mid, self.ln2.w, self.ln2.b, self.ln2.eps)
+            x, resid2 = ops.pair_layer_norm_fork(resid_mid, self.ln2.w, self.ln2.b, self.ln2.eps, prefetch=pf2)
             done = ops.pair_mlp_in(x, mlp.W_in, mlp.b_in, erf=erf, index=ps[0]) if len(ps) == 1 else None
             if done is not None:  # the splice inside the producing op (sparse copy + masked dpre)
                 _, post = done
@@ -627,7 +638,7 @@ class TransformerBlock(nn.Module):
         if self.cfg.attn_only:
             return resid_mid
         mlp = self.mlp
-        x, resid_mid = self._norm_fork(self.ln2, resid_mid, run)
+        x, resid_mid = self._norm_fork(self.ln2, resid_mid, run, self._fwd_prefetch(ops, mlp.W_in, mlp.W_out))
         return ops.mlp_gelu_residual(x, mlp.W_in, mlp.b_in, mlp.W_out, mlp.b_out, resid_mid)
 
 

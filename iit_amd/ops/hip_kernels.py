@@ -45,6 +45,8 @@ _SIGS = {
     "iit_embed_pos_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "iit_embed_pos_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "iit_ln_fwd": [c_void_p] * 7 + [c_int, c_int, c_float, c_ull, c_int, c_int, c_void_p],
+    "iit_ln_fwd_pf": [c_void_p] * 7 + [c_int, c_int, c_float, c_ull, c_int, c_int, c_void_p, c_long, c_void_p, c_long,
+                      c_int, c_void_p],
     "iit_ln_bwd": [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 10 + [c_int, c_int, c_int, c_ull, c_int, c_void_p],
     "iit_ln_bwd_part_rows": [],
     "iit_attn_small_fwd": [c_void_p] * 4 + [c_ull, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_float, c_int,
@@ -647,27 +649,57 @@ def embed_pos_bwd(tokens, g, dWE, dWpos, B, S, d):
     _check(lib().iit_embed_pos_bwd(_p(tokens), _p(g), _p(dWE), _p(dWpos), B, S, d, _stream()), "embed_pos_bwd")
 
 
-def _ln_fwd(what, x, w, b, y, y32, mean, rstd, T, d, eps, pos_mask=0, S=1, Tb=0) -> int:
+def prefetch_wgs(nbytes: int, per_mb: float) -> int:
+    """Workgroups that prefetch ``nbytes`` at ``per_mb`` workgroups per MiB: 0 without a whole 64-byte granule or
+    with no density, else at least one and never more than there are granules (or than 1024)."""
+    gran = int(nbytes) // 64
+    if gran <= 0 or per_mb <= 0:
+        return 0
+    return max(1, min(1024, gran, int(nbytes / 2 ** 20 * per_mb)))
+
+
+def _ln_prefetch_args(prefetch, wgs):
+    """``(p0, bytes0, p1, bytes1, wgs)`` of ``iit_ln_fwd_pf`` for up to two tensors (whole 64-byte granules of each);
+    ``wgs``: the workgroup count, None = :func:`prefetch_wgs` at the dual launches' density."""
+    ts = [t for t in (prefetch or ()) if t is not None and t.is_cuda and t.is_contiguous()][:2]
+    nb = [t.numel() * t.element_size() // 64 * 64 for t in ts]
+    if wgs is None:
+        wgs = prefetch_wgs(sum(nb), _PF_PER_MB)
+    if not any(nb) or wgs <= 0:
+        return (None, 0, None, 0, 0)
+    ts += [None] * (2 - len(ts))
+    nb += [0] * (2 - len(nb))
+    return (_p(ts[0]), nb[0], _p(ts[1]), nb[1], int(wgs))
+
+
+def _ln_fwd(what, x, w, b, y, y32, mean, rstd, T, d, eps, pos_mask=0, S=1, Tb=0, prefetch=None,
+            pf_wgs=None) -> int:
     if CHECK_BOUNDS:
         _bounds(what, ("x", x, T, d, d), ("y", y, T, d, d), ("y32", y32, T, d, d), ("mean", mean, 1, T, T),
                 ("rstd", rstd, 1, T, T))
-    return lib().iit_ln_fwd(_p(x), _p(w), _p(b), _p(y), _p(y32), _p(mean), _p(rstd), T, d, eps, pos_mask, S, Tb, _stream())
+    return lib().iit_ln_fwd_pf(_p(x), _p(w), _p(b), _p(y), _p(y32), _p(mean), _p(rstd), T, d, eps, pos_mask, S, Tb,
+                               *_ln_prefetch_args(prefetch, pf_wgs), _stream())
 
 
-def ln_fwd(x, w, b, y, mean, rstd, T, d, eps):
-    _check(_ln_fwd("ln_fwd", x, w, b, y, None, mean, rstd, T, d, eps), "ln_fwd")
+# ``prefetch`` of the LN forwards: up to two tensors (the bf16 mirrors of the weights the following GEMMs read) that
+# extra workgroups of the launch read into the caches (csrc/layer_norm.hip); ``pf_wgs`` overrides their number
+def ln_fwd(x, w, b, y, mean, rstd, T, d, eps, prefetch=None, pf_wgs=None):
+    _check(_ln_fwd("ln_fwd", x, w, b, y, None, mean, rstd, T, d, eps, prefetch=prefetch, pf_wgs=pf_wgs),
+           "ln_fwd")
 
 
-def ln_fwd_twin(x, w, b, y, y32, mean, rstd, T, d, eps) -> bool:
+def ln_fwd_twin(x, w, b, y, y32, mean, rstd, T, d, eps, prefetch=None, pf_wgs=None) -> bool:
     """``ln_fwd`` that also writes ``y32`` = fp32(y) in the same pass; False when the vector layout does not apply
     (nothing launched: the caller casts)."""
-    return _ln_fwd("ln_fwd_twin", x, w, b, y, y32, mean, rstd, T, d, eps) == 0
+    return _ln_fwd("ln_fwd_twin", x, w, b, y, y32, mean, rstd, T, d, eps, prefetch=prefetch,
+                   pf_wgs=pf_wgs) == 0
 
 
-def ln_fwd_sel(x, w, b, y, mean, rstd, T, d, eps, pos_mask: int, S: int, Tb: int):
+def ln_fwd_sel(x, w, b, y, mean, rstd, T, d, eps, pos_mask: int, S: int, Tb: int, prefetch=None, pf_wgs=None):
     """``ln_fwd`` over paired rows with the whole-position splice inside the kernel: base rows [0, Tb) at positions
     whose bit is set in ``pos_mask`` normalise the source row ``row + Tb`` (csrc/layer_norm.hip RowSel)."""
-    _check(_ln_fwd("ln_fwd_sel", x, w, b, y, None, mean, rstd, T, d, eps, pos_mask, S, Tb), "ln_fwd_sel")
+    _check(_ln_fwd("ln_fwd_sel", x, w, b, y, None, mean, rstd, T, d, eps, pos_mask, S, Tb, prefetch=prefetch,
+                   pf_wgs=pf_wgs), "ln_fwd_sel")
 
 
 _LN_PART_ROWS = [0]

@@ -428,6 +428,23 @@ class EmbedPosFn(Function):
         return None, None, None
 
 
+# ---- forward weight prefetch from the LN launches (profiles/fwd_weight_prefetch_ab.txt): the bf16 weights of the GEMMs
+# that follow a norm are HBM-cold after the optimizer pass; the norm's launch reads them into the caches with extra
+# workgroups (csrc/layer_norm.hip).  The tensors are no autograd inputs, so they reach the forward beside the
+# Function's arguments: the slot holds them for the duration of one ``apply``.
+_LN_PF: list = [None]
+
+
+def _ln_apply(fn, prefetch, *args):
+    """``fn.apply(*args)`` for an LN Function, whose forward launch prefetches ``prefetch`` (up to two tensors, or
+    None: :meth:`HipOps.fwd_prefetch`)."""
+    _LN_PF[0] = prefetch
+    try:
+        return fn.apply(*args)
+    finally:
+        _LN_PF[0] = None
+
+
 def _xhat16(w, b, d: int) -> bool:
     """The LN backward reads the forward's bf16 output as xhat (norms without weight and bias: 2 B per element instead
     of the fp32 input).  Round 3 reverted it over a staged-backward mismatch that round 4 traced to the split-store GEMM
@@ -440,8 +457,10 @@ def _ln_forward(ctx, x, w, b, eps, x_full=None, twin=False, xhat16=False, pos_ma
     source rows) for the paired classes -- that saves the base rows for the backward: their fp32 input, or with
     ``xhat16`` their bf16 output.  Returns ``(y, y32)`` in the shape of the rows' tensor; ``y32`` (``twin``) is the fp32
     image of ``y`` from the same pass, None otherwise.  Both are allocated in that shape (outputs that are views
-    could not be modified in place downstream of a multi-output Function), except with ``xhat16`` (the Fork classes)."""
+    could not be modified in place downstream of a multi-output Function), except with ``xhat16`` (the Fork classes).
+    The launch also reads the weights of :func:`_ln_apply`'s ``prefetch`` into the caches."""
     ctx.set_materialize_grads(False)
+    prefetch = _LN_PF[0]
     rows = x if x_full is None else x_full
     lead, d = rows.shape[:-1], rows.shape[-1]
     x2 = _flat2(rows.float().contiguous())
@@ -460,9 +479,9 @@ def _ln_forward(ctx, x, w, b, eps, x_full=None, twin=False, xhat16=False, pos_ma
     mean = torch.empty(T2, dtype=F32, device=x.device)
     rstd = torch.empty(T2, dtype=F32, device=x.device)
     if pos_mask:  # whole-position splice of the base rows from the source rows, inside the LN kernel
-        K.ln_fwd_sel(x2, w, b, yf, mean, rstd, T2, d, eps, pos_mask, S, T)
-    elif not twin or not K.ln_fwd_twin(x2, w, b, yf, y32.view(T2, d), mean, rstd, T2, d, eps):
-        K.ln_fwd(x2, w, b, yf, mean, rstd, T2, d, eps)
+        K.ln_fwd_sel(x2, w, b, yf, mean, rstd, T2, d, eps, pos_mask, S, T, prefetch=prefetch)
+    elif not twin or not K.ln_fwd_twin(x2, w, b, yf, y32.view(T2, d), mean, rstd, T2, d, eps, prefetch=prefetch):
+        K.ln_fwd(x2, w, b, yf, mean, rstd, T2, d, eps, prefetch=prefetch)
         if twin:
             y32.copy_(y)
     ctx.save_for_backward((yf if xhat16 else x2)[:T], mean[:T], rstd[:T])
@@ -1607,18 +1626,26 @@ class HipOps(TorchOps):
         # profiles/dual_l2_hypothesis_r6.txt)
         pol = os.environ.get("IIT_DUAL_PREFETCH", "auto")
         self.prefetch = pol == "1" or (pol == "auto" and type(model).__name__ != "HookedEncoder")
+        self.fwd_pf = False  # forward weight prefetch from the LN launches, set per forward (begin_forward)
         self._layer_of = {}
+        self._mirror_key = {}  # id(matrix) -> its key in the layer's shadow dict
         for i, blk in enumerate(model.blocks):
-            self._layer_of[id(blk.attn.W_Q)] = i
-            self._layer_of[id(blk.attn.W_O)] = i
+            mats = [(blk.attn.W_Q, "qkv"), (blk.attn.W_O, "o")]
             if not model.cfg.attn_only:
-                self._layer_of[id(blk.mlp.W_in)] = i
-                self._layer_of[id(blk.mlp.W_out)] = i
+                mats += [(blk.mlp.W_in, "in"), (blk.mlp.W_out, "out")]
+            for W, key in mats:
+                self._layer_of[id(W)] = i
+                self._mirror_key[id(W)] = key
 
     def begin_forward(self):
         self.shadow.ensure()
         _PF_SEQ.clear()  # a new forward: the prefetch order restarts (the references of the last one are dropped)
         _PF_ON[0] = self.prefetch
+        # forward weight prefetch (IIT_FWD_PREFETCH=auto|0|1): LN1 / LN2 of a block read the bf16 weights of the GEMMs
+        # after them into the caches -- HBM-cold after the optimizer pass, which costs the forward GEMMs their
+        # isolated time (profiles/fwd_weight_prefetch_ab.txt).  auto = HookedTransformer only: the only family measured
+        pol = os.environ.get("IIT_FWD_PREFETCH", "auto")
+        self.fwd_pf = pol == "1" or (pol == "auto" and type(self.model).__name__ == "HookedTransformer")
 
     def _L(self, p):
         return self.shadow.layers[self._layer_of[id(p)]]
@@ -1640,21 +1667,29 @@ class HipOps(TorchOps):
         """Small parameters used outside the fused kernels (BERT token types, pooler, classifier)."""
         return p.to(BF16)
 
-    def layer_norm(self, x, w, b, eps):
-        return LayerNormFn.apply(x, w, b, eps)
+    def fwd_prefetch(self, *Ws):
+        """The bf16 compute copies of the block matrices ``Ws`` (the B operands of the forward GEMMs that follow a
+        norm) for that norm's ``prefetch=``, or None when the forward weight prefetch is off (``IIT_FWD_PREFETCH``)."""
+        if not self.fwd_pf:
+            return None
+        return tuple(self._L(W)[self._mirror_key[id(W)]] for W in Ws)
 
-    def layer_norm_twin(self, x, w, b, eps):
+    # ``prefetch`` of the norms: :meth:`fwd_prefetch` of the weights that the GEMMs after the norm read
+    def layer_norm(self, x, w, b, eps, prefetch=None):
+        return _ln_apply(LayerNormFn, prefetch, x, w, b, eps)
+
+    def layer_norm_twin(self, x, w, b, eps, prefetch=None):
         """``layer_norm`` whose bf16 output carries an fp32 twin for residual consumers (:class:`LayerNormTwinFn`;
         ``IIT_LN_TWIN=0`` disables)."""
         if os.environ.get("IIT_LN_TWIN", "1") == "0":
-            return LayerNormFn.apply(x, w, b, eps)
-        y, y32 = LayerNormTwinFn.apply(x, w, b, eps)
+            return _ln_apply(LayerNormFn, prefetch, x, w, b, eps)
+        y, y32 = _ln_apply(LayerNormTwinFn, prefetch, x, w, b, eps)
         y._iit_f32 = (y.data_ptr(), y._version, y32)
         return y
 
-    def layer_norm_fork(self, x, w, b, eps):
+    def layer_norm_fork(self, x, w, b, eps, prefetch=None):
         """``(LN(x), x_passthrough)``; use the passthrough for the skip connection."""
-        return LayerNormForkFn.apply(x, w, b, eps)
+        return _ln_apply(LayerNormForkFn, prefetch, x, w, b, eps)
 
     # -- attention -------------------------------------------------------------------
     def qkv(self, x, W_Q, W_K, W_V, b_Q, b_K, b_V):
@@ -1781,23 +1816,23 @@ class HipOps(TorchOps):
         out, full = _one(EmbedPosPairFn, tokens, W_E, W_pos, full_tok)
         return Paired(out, full)
 
-    def pair_layer_norm_fork(self, p: Paired, w, b, eps):
+    def pair_layer_norm_fork(self, p: Paired, w, b, eps, prefetch=None):
         """(LN of both row sets, residual passthrough): ``(Paired normed, Paired resid)``."""
         box = []
-        y, x_pass = LayerNormForkPairFn.apply(p.base, w, b, eps, p.full.float().contiguous(), box)
+        y, x_pass = _ln_apply(LayerNormForkPairFn, prefetch, p.base, w, b, eps, p.full.float().contiguous(), box)
         return Paired(y, box[0]), Paired(x_pass, p.full)
 
-    def pair_layer_norm(self, p: Paired, w, b, eps, pos_mask: int = 0, twin: bool = False) -> Paired:
+    def pair_layer_norm(self, p: Paired, w, b, eps, pos_mask: int = 0, twin: bool = False, prefetch=None) -> Paired:
         """LN of both row sets (no residual passthrough: post-LN blocks).  ``pos_mask``: the base rows at these
         positions take the source rows' output -- an interchange splice of whole positions of the LN output done
         by the LN kernel itself (and masked out of its backward), no separate splice pass."""
         box = []
         if twin and not pos_mask and w is not None and os.environ.get("IIT_LN_TWIN", "1") != "0":
-            y, y32 = LayerNormPairTwinFn.apply(p.base, w, b, eps, p.full.float().contiguous(), box)
+            y, y32 = _ln_apply(LayerNormPairTwinFn, prefetch, p.base, w, b, eps, p.full.float().contiguous(), box)
             yf, yf32 = box[0]
             y._iit_f32 = (y.data_ptr(), y._version, y32)  # (the unpaired blocks after the pairing ends)
             return Paired(y, yf, (y32, yf32))
-        y = LayerNormPairFn.apply(p.base, w, b, eps, p.full.float().contiguous(), box, int(pos_mask))
+        y = _ln_apply(LayerNormPairFn, prefetch, p.base, w, b, eps, p.full.float().contiguous(), box, int(pos_mask))
         return Paired(y, box[0])
 
     @staticmethod
