@@ -17,6 +17,7 @@
 // k-major in place (ConvWTStager):  dx[n][h][w][ci] = sum_{kh, kw, co} dy[n][(h + pad - kh) / s][(w + pad - kw) / s][co]
 // W[co][kh][kw][ci] over the taps where the division is exact (stride 2: the other taps read the zero page).
 #include "gemm_glds_body.h"
+#include "gemm_tiles.h"
 
 namespace {
 
@@ -235,52 +236,35 @@ hipError_t launch_conv(const G2Args& a, int splits, hipStream_t s) {
   return hipGetLastError();
 }
 
-// tiles (BM, BN, ring depth, waves, workgroups per CU): the output is [N H W][Cout] with Cout 64..512
-constexpr int kConvTiles = 6;
-const int kConvBM[kConvTiles] = {128, 128, 64, 128, 64, 128};
-const int kConvBN[kConvTiles] = {64, 128, 64, 128, 128, 64};
-
+// one launch per row of IIT_CONV_TILE_LIST (csrc/gemm_tiles.h)
 hipError_t launch_conv_tile(const G2Args& a, int tile, int splits, hipStream_t s) {
   switch (tile) {
-    case 0: return launch_conv<128, 64, 4>(a, splits, s);
-    case 1: return launch_conv<128, 128, 3>(a, splits, s);
-    case 2: return launch_conv<64, 64, 4, 4, 2>(a, splits, s);
-    case 3: return launch_conv<128, 128, 2, 4, 2>(a, splits, s);
-    case 4: return launch_conv<64, 128, 2, 4, 3>(a, splits, s);
-    case 5: return launch_conv<128, 64, 2, 4, 2>(a, splits, s);
+#define X(ID, BM, BN, NS, NW, OCC) \
+  case ID: return launch_conv<BM, BN, NS, NW, OCC>(a, splits, s);
+    IIT_CONV_TILE_LIST(X)
+#undef X
     default: return hipErrorInvalidValue;
   }
 }
 
-// weight-gradient tiles (BM = Cout rows, BN = channels of one tap, ring depth)
-constexpr int kWgTiles = 4;
-const int kWgBM[kWgTiles] = {64, 128, 128, 64};
-const int kWgBN[kWgTiles] = {64, 64, 128, 128};
-
+// the weight gradient: one launch per row of IIT_CONV_WG_TILE_LIST
 template <int EPI>
 hipError_t launch_wgrad(const G2Args& a, int tile, int splits, hipStream_t s) {
   const dim3 block(256);
-#define WG(T, BM_, BN_, NS_)                                                                                 \
-  case T:                                                                                                   \
-    hipLaunchKernelGGL((conv3x3_wgrad_kernel<BM_, BN_, NS_, 4, 1, EPI>), dim3((a.M / BM_) * (a.N / BN_), splits), \
-                       block, 0, s, a);                                                                     \
-    break;
   switch (tile) {
-    WG(0, 64, 64, 4)
-    WG(1, 128, 64, 4)
-    WG(2, 128, 128, 3)
-    WG(3, 64, 128, 4)
+#define X(ID, BM, BN, NS)                                                                                     \
+  case ID:                                                                                                    \
+    hipLaunchKernelGGL((conv3x3_wgrad_kernel<BM, BN, NS, 4, 1, EPI>), dim3((a.M / BM) * (a.N / BN), splits), \
+                       block, 0, s, a);                                                                       \
+    break;
+    IIT_CONV_WG_TILE_LIST(X)
+#undef X
     default: return hipErrorInvalidValue;
   }
-#undef WG
   return hipGetLastError();
 }
 
 }  // namespace
-
-IIT_EXPORT int iit_conv3x3_tiles() { return kConvTiles; }
-IIT_EXPORT int iit_conv3x3_wgrad_tiles() { return kWgTiles; }
-IIT_EXPORT int iit_conv3x3_rows(int tile) { return tile >= 0 && tile < kConvTiles ? kConvBM[tile] : 0; }
 
 // the forward convolution (kernel k, stride s, padding pad) maps an SH x SW image to OH x OW
 static bool conv_geom_ok(long N, int SH, int SW, int OH, int OW, int k, int s, int pad) {
@@ -295,10 +279,11 @@ static bool conv_geom_ok(long N, int SH, int SW, int OH, int OW, int k, int s, i
 // N OH OW % BM == 0 (no partial row tiles), k k Cs % (64 splits) == 0 (equal K ranges)
 IIT_EXPORT int iit_conv2d_ok(long N, int SH, int SW, int Cs, int OH, int OW, int Co, int k, int s, int pad,
                              int transposed, int tile, int splits) {
-  if (tile < 0 || tile >= kConvTiles || Cs <= 0 || Co <= 0 || splits < 1) return 0;
+  const TileRow* t = find_tile(kConvRows, tile);
+  if (!t || Cs <= 0 || Co <= 0 || splits < 1) return 0;
   if (transposed ? !conv_geom_ok(N, OH, OW, SH, SW, k, s, pad) : !conv_geom_ok(N, SH, SW, OH, OW, k, s, pad)) return 0;
   const long M = N * OH * OW;
-  if (Cs % 64 || Co % kConvBN[tile] || M % kConvBM[tile] || M >= (1L << 31)) return 0;
+  if (Cs % 64 || Co % t->bn || M % t->bm || M >= (1L << 31)) return 0;
   if ((k * k * Cs) % (64 * splits)) return 0;
   return 1;
 }
@@ -348,9 +333,10 @@ IIT_EXPORT int iit_conv2d(const void* x, const void* w, void* y, const void* zer
 // Cin % BN, N OH OW % (64 splits) == 0
 IIT_EXPORT int iit_conv2d_wgrad_ok(long N, int SH, int SW, int Cin, int OH, int OW, int Cout, int k, int s, int pad,
                                    int tile, int splits) {
-  if (tile < 0 || tile >= kWgTiles || splits < 1 || Cin % 64 || !conv_geom_ok(N, SH, SW, OH, OW, k, s, pad)) return 0;
+  const TileRow* t = find_tile(kConvWgRows, tile);
+  if (!t || splits < 1 || Cin % 64 || !conv_geom_ok(N, SH, SW, OH, OW, k, s, pad)) return 0;
   const long K = N * OH * OW;
-  if (Cout % kWgBM[tile] || Cin % kWgBN[tile] || K % (64L * splits) || K >= (1L << 24)) return 0;
+  if (Cout % t->bm || Cin % t->bn || K % (64L * splits) || K >= (1L << 24)) return 0;
   return 1;
 }
 
@@ -386,25 +372,4 @@ IIT_EXPORT int iit_conv2d_wgrad(const void* dy, const void* x, float* dw, const 
   a.conv_pad = pad;
   hipStream_t st = (hipStream_t)stream;
   return (int)(acc ? launch_wgrad<E_F32_ACC>(a, tile, splits, st) : launch_wgrad<E_F32_STORE>(a, tile, splits, st));
-}
-
-// the 3 x 3 / stride-1 / pad-1 entry points (same image size in and out)
-IIT_EXPORT int iit_conv3x3_ok(long N, int H, int W, int Cin, int Cout, int tile, int splits) {
-  return iit_conv2d_ok(N, H, W, Cin, H, W, Cout, 3, 1, 1, 0, tile, splits);
-}
-
-IIT_EXPORT int iit_conv3x3(const void* x, const void* w, void* y, const void* zero, long N, int H, int W, int Cin,
-                           int Cout, int flip, int tile, int splits, float* ws, int* counters, float* cstat,
-                           void* stream) {
-  return iit_conv2d(x, w, y, zero, N, H, W, Cin, H, W, Cout, 3, 1, 1, flip, tile, splits, ws, counters, cstat, stream);
-}
-
-IIT_EXPORT int iit_conv3x3_wgrad_ok(long N, int H, int W, int Cin, int Cout, int tile, int splits) {
-  return iit_conv2d_wgrad_ok(N, H, W, Cin, H, W, Cout, 3, 1, 1, tile, splits);
-}
-
-IIT_EXPORT int iit_conv3x3_wgrad(const void* dy, const void* x, float* dw, const void* zero, long N, int H, int W,
-                                 int Cin, int Cout, int acc, int tile, int splits, float* ws, int* counters,
-                                 void* stream) {
-  return iit_conv2d_wgrad(dy, x, dw, zero, N, H, W, Cin, H, W, Cout, 3, 1, 1, acc, tile, splits, ws, counters, stream);
 }

@@ -19,9 +19,13 @@
 // kmaj_swz, unchanged): k-contiguous operands [256][64] with 16-B chunk c of row r at slot c ^ ((r >> 1) & 7) --
 // a 32x32x16 fragment (32 rows, 2 chunks) then touches 16 distinct 16-B slots per ds_read_b128 lane group
 // (conflict-free); k-major operands [64][256] as four 64-column panels read with ds_read_b64_tr_b16.
+#include "gemm_tiles.h"
 #include "gemm_w4.h"
 
 namespace {
+
+constexpr bool is_w4_row(const TileRow* r) { return r && r->bm == W4_BM && r->bn == W4_BN && r->nw == W4_NW; }
+static_assert(is_w4_row(find_tile(kGldsRows, 41)) && is_w4_row(find_tile(kGldsRows, 42)), "tiles 41 / 42 as published");
 
 template <bool AKM, bool BKM, int EPI, int BK>
 __global__ __launch_bounds__(W4_NT, 1) void gemm_4w_kernel(G2Args p) {

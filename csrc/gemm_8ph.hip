@@ -28,6 +28,7 @@
 //    flight, everything of K-tile t + 1 has landed -- before the barrier ending that L-segment; K-tile t + 1 is
 //    first read in the next L-segment of either group, after that barrier.
 #include "gemm_glds_body.h"
+#include "gemm_tiles.h"
 
 namespace {
 
@@ -39,6 +40,8 @@ constexpr int P8_ECH = 2;                  // epilogue row chunks (128 rows each
 constexpr int P8_EPI_BYTES = P8_BM / P8_ECH * P8_EPS * 4;
 constexpr int P8_BYTES = 2 * P8_BUF > P8_EPI_BYTES ? 2 * P8_BUF : P8_EPI_BYTES;
 static_assert(P8_BYTES <= 160 * 1024, "LDS budget");
+constexpr TileRow kP8Row = *find_tile(kGldsRows, 40);  // the row gemm_tiles.h publishes for this kernel
+static_assert(kP8Row.bm == P8_BM && kP8Row.bn == P8_BN && kP8Row.bk == P8_BK && kP8Row.nw == P8_NW, "tile 40");
 
 // runtime vmcnt(2 n) for n = 0..5 (an immediate is required; 2 LDS-DMA per half-tile)
 __device__ __forceinline__ void wait_halves(int n) {

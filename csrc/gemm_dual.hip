@@ -11,6 +11,7 @@
 // the dW tiles (split-major, so the K-splits of a tile are a launch round apart and its reduction ticket is taken
 // late), the rest the dX tiles.  The dW problem comes first because its K (the token count) is the longer loop.
 #include "gemm_glds_body.h"
+#include "gemm_tiles.h"
 #include "prefetch.h"
 
 namespace {
@@ -49,28 +50,6 @@ __global__ __launch_bounds__(TW::NW * 64, TW::OCC) void gemm_dual_kernel(G2Args 
   }
 }
 
-// Two families of tiles (a launch takes both of its tiles from one family):
-// * 4 waves, two workgroups per CU: dW 128x96, 128x128, 96x96, 64x96, 64x64; dX 128x96, 64x96, 128x192, 128x128 --
-//   one problem's prologue / epilogue under the other's main loop on the same CU;
-// * 8 waves (two per SIMD), one workgroup per CU: dW 256x128, 128x128, dX 256x192, 256x128, 128x128 -- the big
-//   tiles that run the
-//   paired forward at ~1 PF/s (fewer operand bytes per flop than 128x128), which alone leave most of the CUs idle on a
-//   [768][N] weight gradient; here the dX tiles fill them.  (A 256x192 dW tile spills registers: not offered.)
-// (index -> the single-launch tile id of the same shape, for the shape checks)
-// * 4 waves, one workgroup per CU, deep rings (3-4 K-tiles, up to 128 KiB): dW 128x128, 128x96, dX 128x128,
-//   128x192 -- more operand bytes in flight for the operands that come cold from HBM inside the step (the
-//   activations saved by the forward), where the two-stage rings of the two-per-CU tiles wait on the fill.
-constexpr int kWTiles = 9, kXTiles = 9;
-const int kWTileId[kWTiles] = {23, 25, 26, 24, 3, 7, 6, 4, 13};
-const int kXTileId[kXTiles] = {23, 24, 27, 25, 5, 7, 6, 4, 22};
-const int kWBM[kWTiles] = {128, 128, 96, 64, 64, 256, 128, 128, 128};
-const int kWBN[kWTiles] = {96, 128, 96, 96, 64, 128, 128, 128, 96};
-const int kXBM[kXTiles] = {128, 64, 128, 128, 256, 256, 128, 128, 128};
-const int kXBN[kXTiles] = {96, 96, 192, 128, 192, 128, 128, 128, 192};
-// tile family: 0 = 4 waves x 2 per CU, 1 = 8 waves x 1 per CU, 2 = 4 waves x 1 per CU with deep rings
-__host__ __device__ constexpr int w_family(int t) { return t >= 7 ? 2 : (t >= 5 ? 1 : 0); }
-__host__ __device__ constexpr int x_family(int t) { return t >= 7 ? 2 : (t >= 4 ? 1 : 0); }
-
 template <class TW, int EW, class TX, int EX>
 hipError_t launch2(const G2Args& w, const G2Args& x, int w_splits, const Prefetch& pf, hipStream_t s) {
   const int wt = (w.M / TW::BM) * (w.N / TW::BN), xt = (x.M / TX::BM) * (x.N / TX::BN);
@@ -79,45 +58,30 @@ hipError_t launch2(const G2Args& w, const G2Args& x, int w_splits, const Prefetc
   return hipGetLastError();
 }
 
+// the dX tile: the rows of IIT_DUAL_X_TILE_LIST (csrc/gemm_tiles.h) whose (NW, OCC) are the dW tile's
 template <class TW, int EW, int EX>
 hipError_t pick_x(const G2Args& w, const G2Args& x, int w_splits, int xtile, const Prefetch& pf, hipStream_t s) {
-  if constexpr (TW::NW == 4 && TW::OCC == 1) {
-    switch (xtile) {
-      case 7: return launch2<TW, EW, Cfg<128, 128, 4, 4, 1>, EX>(w, x, w_splits, pf, s);
-      case 8: return launch2<TW, EW, Cfg<128, 192, 3, 4, 1>, EX>(w, x, w_splits, pf, s);
-      default: return hipErrorInvalidValue;
-    }
-  } else if constexpr (TW::NW == 4) {
-    switch (xtile) {
-      case 0: return launch2<TW, EW, Cfg<128, 96, 2>, EX>(w, x, w_splits, pf, s);
-      case 1: return launch2<TW, EW, Cfg<64, 96, 3>, EX>(w, x, w_splits, pf, s);
-      case 2: return launch2<TW, EW, Cfg<128, 192, 2>, EX>(w, x, w_splits, pf, s);
-      case 3: return launch2<TW, EW, Cfg<128, 128, 2>, EX>(w, x, w_splits, pf, s);
-      default: return hipErrorInvalidValue;
-    }
-  } else {
-    switch (xtile) {
-      case 4: return launch2<TW, EW, Cfg<256, 192, 2, 8, 1>, EX>(w, x, w_splits, pf, s);
-      case 5: return launch2<TW, EW, Cfg<256, 128, 2, 8, 1>, EX>(w, x, w_splits, pf, s);
-      case 6: return launch2<TW, EW, Cfg<128, 128, 4, 8, 1>, EX>(w, x, w_splits, pf, s);
-      default: return hipErrorInvalidValue;
-    }
+  switch (xtile) {
+#define X(IDX, BM_, BN_, NS_, NW_, OCC_, GLDS)                                          \
+  case IDX:                                                                             \
+    if constexpr (TW::NW == NW_ && TW::OCC == OCC_)                                     \
+      return launch2<TW, EW, Cfg<BM_, BN_, NS_, NW_, OCC_>, EX>(w, x, w_splits, pf, s); \
+    break;
+    IIT_DUAL_X_TILE_LIST(X)
+#undef X
   }
+  return hipErrorInvalidValue;
 }
 
+// the dW tile: one row of IIT_DUAL_W_TILE_LIST
 template <int EW, int EX>
 hipError_t pick_w(const G2Args& w, const G2Args& x, int w_splits, int wtile, int xtile, const Prefetch& pf,
                   hipStream_t s) {
   switch (wtile) {
-    case 0: return pick_x<Cfg<128, 96, 2>, EW, EX>(w, x, w_splits, xtile, pf, s);
-    case 1: return pick_x<Cfg<128, 128, 2>, EW, EX>(w, x, w_splits, xtile, pf, s);
-    case 2: return pick_x<Cfg<96, 96, 3>, EW, EX>(w, x, w_splits, xtile, pf, s);
-    case 3: return pick_x<Cfg<64, 96, 3>, EW, EX>(w, x, w_splits, xtile, pf, s);
-    case 4: return pick_x<Cfg<64, 64, 4>, EW, EX>(w, x, w_splits, xtile, pf, s);
-    case 5: return pick_x<Cfg<256, 128, 2, 8, 1>, EW, EX>(w, x, w_splits, xtile, pf, s);
-    case 6: return pick_x<Cfg<128, 128, 4, 8, 1>, EW, EX>(w, x, w_splits, xtile, pf, s);
-    case 7: return pick_x<Cfg<128, 128, 4, 4, 1>, EW, EX>(w, x, w_splits, xtile, pf, s);
-    case 8: return pick_x<Cfg<128, 96, 4, 4, 1>, EW, EX>(w, x, w_splits, xtile, pf, s);
+#define X(IDX, BM, BN, NS, NW, OCC, GLDS) \
+  case IDX: return pick_x<Cfg<BM, BN, NS, NW, OCC>, EW, EX>(w, x, w_splits, xtile, pf, s);
+    IIT_DUAL_W_TILE_LIST(X)
+#undef X
     default: return hipErrorInvalidValue;
   }
 }
@@ -128,29 +92,25 @@ extern "C" int iit_gemm_glds_ok(const void* A, const void* B, const void* C, con
                                 long lda, long ldb, long ldc, long ldc2, long ldr, int M, int N, int K, int mode,
                                 int epi, int bias_cols, int tile, int splits, int reduce);
 
-IIT_EXPORT int iit_gemm_dual_tiles(int* w_tiles, int* x_tiles) {
-  *w_tiles = kWTiles;
-  *x_tiles = kXTiles;
-  return 0;
-}
-
 // 1 when the pair (dW problem on dual tile ``wtile`` with ``wsplits`` K-splits -- reduction split when ``reduce`` --,
 // dX problem on dual tile ``xtile``) is covered by the dual kernel
 IIT_EXPORT int iit_gemm_dual_ok(const void* wA, const void* wB, const void* wC, long wlda, long wldb, long wldc, int wM,
                                 int wN, int wK, int wepi, int wtile, int wsplits, int reduce, const void* xA,
                                 const void* xB, const void* xC, const void* xC2, long xlda, long xldb, long xldc,
                                 long xldc2, int xM, int xN, int xK, int xepi, int xtile) {
-  if (wtile < 0 || wtile >= kWTiles || xtile < 0 || xtile >= kXTiles || w_family(wtile) != x_family(xtile)) return 0;
+  const TileRow* wt = find_tile(kDualWRows, wtile);
+  const TileRow* xt = find_tile(kDualXRows, xtile);
+  if (!wt || !xt || wt->nw != xt->nw || wt->occ != xt->occ) return 0;  // one launch geometry for both problems
   if (!(wepi == E_F32_STORE || wepi == E_F32_ACC) || !(xepi == E_BF16 || xepi == E_DGELU)) return 0;
-  if (!iit_gemm_glds_ok(wA, wB, wC, nullptr, nullptr, wlda, wldb, wldc, 0, 0, wM, wN, wK, 3, wepi, 0,
-                        kWTileId[wtile], wsplits, reduce))
+  if (!iit_gemm_glds_ok(wA, wB, wC, nullptr, nullptr, wlda, wldb, wldc, 0, 0, wM, wN, wK, 3, wepi, 0, wt->aux,
+                        wsplits, reduce))
     return 0;
   if (!iit_gemm_glds_ok(xA, xB, xC, xepi == E_DGELU ? xC2 : nullptr, nullptr, xlda, xldb, xldc, xldc2, 0, xM, xN, xK,
-                        0, xepi, 0, kXTileId[xtile], 1, 0))
+                        0, xepi, 0, xt->aux, 1, 0))
     return 0;
   // the dW tiles' XCD-local order needs their count to be a multiple of the 8 XCDs only for locality, not for
   // correctness; the grid must stay within one dimension
-  const long wg = (long)(wM / kWBM[wtile]) * (wN / kWBN[wtile]) * wsplits + (long)(xM / kXBM[xtile]) * (xN / kXBN[xtile]);
+  const long wg = (long)(wM / wt->bm) * (wN / wt->bn) * wsplits + (long)(xM / xt->bm) * (xN / xt->bn);
   return wg > 0 && wg < (1L << 31) ? 1 : 0;
 }
 

@@ -13,6 +13,7 @@
 //     of the stored values); ``bias0`` is not read at or beyond N.
 // M and K stay multiples of the tile; one K split.  iit_gemm_edge_plan exposes the edge arithmetic to the host.
 #include "gemm_glds_body.h"
+#include "gemm_tiles.h"
 
 namespace {
 
@@ -73,23 +74,29 @@ hipError_t launch(const G2Args& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// the edge-capable tiles, under the tile ids (and with the ring depths / occupancy) they have in gemm_glds.hip
+// one launch per row of IIT_EDGE_TILE_LIST (csrc/gemm_tiles.h): the edge-capable tiles, under the tile ids (and with
+// the ring depths / occupancy, asserted there) they have in gemm_glds.hip
 template <bool AKM, int EPI>
 hipError_t launch_tile(const G2Args& a, int tile, hipStream_t s) {
   switch (tile) {
-    case 0: return launch<128, 128, 3, AKM, EPI>(a, s);
-    case 7: return launch<256, 128, 2, AKM, EPI, 8>(a, s);
-    case 25: return launch<128, 128, 2, AKM, EPI, 4, 2>(a, s);
+#define X(ID, BM, BN, NS, NW, OCC) \
+  case ID: return launch<BM, BN, NS, AKM, EPI, NW, OCC>(a, s);
+    IIT_EDGE_TILE_LIST(X)
+#undef X
     default: return hipErrorInvalidValue;
   }
 }
 
-bool edge_tile(int tile, int* bm, int* bn) {
-  switch (tile) {
-    case 0: case 25: *bm = 128; *bn = 128; return true;
-    case 7: *bm = 256; *bn = 128; return true;
-    default: return false;
-  }
+// the (layout, epilogue) combinations instantiated for every tile: X(mode, A k-major, epilogue)
+#define IIT_EDGE_COMBO_LIST(X) \
+  X(2, false, E_BF16) X(2, false, E_F32_STORE) X(2, false, E_F32_ACC) X(3, true, E_F32_ACC) X(3, true, E_F32_STORE)
+
+constexpr bool combo_ok(int mode, int epi) {
+#define X(MODE, AKM, EPI) \
+  if (mode == (MODE) && epi == (EPI)) return true;
+  IIT_EDGE_COMBO_LIST(X)
+#undef X
+  return false;
 }
 
 inline long pad8l(long n) { return (n + 7) / 8 * 8; }
@@ -103,13 +110,12 @@ inline long pad8l(long n) { return (n + 7) / 8 * 8; }
 // granule that are valid (0: none straddles), one past the last byte touched, one past the operand's last valid
 // byte ((rows - 1) * ld + pad8(N) elements)}.
 IIT_EXPORT int iit_gemm_edge_plan(int rows, int N, long ld, int elem, int tile, long* out6) {
-  int bm, bn;
-  if (!edge_tile(tile, &bm, &bn) || rows <= 0 || N <= 0 || ld < pad8l(N) || (elem != 2 && elem != 4))
-    return (int)hipErrorInvalidValue;
-  const int tiles_n = (N + bn - 1) / bn;
+  const TileRow* t = find_tile(kEdgeRows, tile);
+  if (!t || rows <= 0 || N <= 0 || ld < pad8l(N) || (elem != 2 && elem != 4)) return (int)hipErrorInvalidValue;
+  const int tiles_n = (N + t->bn - 1) / t->bn;
   long used = 0, redirected = 0, straddle = 0, last = 0;
   for (int r = 0; r < rows; ++r)
-    for (int c = 0; c < tiles_n * bn; c += 8) {
+    for (int c = 0; c < tiles_n * t->bn; c += 8) {
       if (edge_redirect(c, N)) {
         redirected += r == 0;
         continue;
@@ -130,11 +136,9 @@ IIT_EXPORT int iit_gemm_edge_plan(int rows, int N, long ld, int elem, int tile, 
 // pad8(N) long
 IIT_EXPORT int iit_gemm_glds_edge_ok(const void* A, const void* B, const void* C, const void* bias0, long lda,
                                      long ldb, long ldc, int M, int N, int K, int mode, int epi, int tile) {
-  int bm, bn;
-  if (!edge_tile(tile, &bm, &bn)) return 0;
-  if (!(mode == 2 || mode == 3)) return 0;
-  if (!(epi == E_F32_ACC || epi == E_F32_STORE || (mode == 2 && epi == E_BF16))) return 0;
-  if (M <= 0 || N <= 0 || K <= 0 || M % bm || K % 64) return 0;
+  const TileRow* t = find_tile(kEdgeRows, tile);
+  if (!t || !combo_ok(mode, epi)) return 0;
+  if (M <= 0 || N <= 0 || K <= 0 || M % t->bm || K % t->bk) return 0;
   if (lda % 8 || ldb % 8 || ldc % 8 || ldb < pad8l(N) || ldc < pad8l(N)) return 0;
   if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)bias0) & 15) return 0;
   return 1;
@@ -155,13 +159,9 @@ IIT_EXPORT int iit_gemm_glds_edge(const void* A, const void* B, void* C, const f
   a.bsum = mode == 3 ? bsum : nullptr;
   a.gsq = epi == E_F32_STORE ? gsq : nullptr;
   hipStream_t s = (hipStream_t)stream;
-#define GE(MODE, AK, EPI) \
-  if (mode == (MODE) && epi == (EPI)) return (int)launch_tile<AK, EPI>(a, tile, s);
-  GE(2, false, E_BF16)
-  GE(2, false, E_F32_STORE)
-  GE(2, false, E_F32_ACC)
-  GE(3, true, E_F32_ACC)
-  GE(3, true, E_F32_STORE)
-#undef GE
+#define X(MODE, AKM, EPI) \
+  if (mode == (MODE) && epi == (EPI)) return (int)launch_tile<AKM, EPI>(a, tile, s);
+  IIT_EDGE_COMBO_LIST(X)
+#undef X
   return (int)hipErrorInvalidValue;
 }

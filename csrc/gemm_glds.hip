@@ -31,6 +31,7 @@
 //   epilogue and, with ``csum``, also reduces the stored dpre tile over its rows in LDS into the b_in gradient
 //   (one atomic per column per tile) -- the separate dgelu pass and the bias column-sum pass disappear.
 #include "gemm_glds_body.h"
+#include "gemm_tiles.h"
 
 namespace {
 
@@ -48,85 +49,39 @@ hipError_t launch(const G2Args& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// tile configurations: (BM, BN, LDS stages)
+// one launch per row of IIT_GLDS_TILE_LIST (csrc/gemm_tiles.h)
 template <bool AKM, bool BKM, int EPI>
 hipError_t launch_tile(const G2Args& a, int tile, hipStream_t s) {
   switch (tile) {
-    case 0: return launch<128, 128, 3, AKM, BKM, EPI>(a, s);
-    case 1: return launch<128, 64, 4, AKM, BKM, EPI>(a, s);
-    case 2: return launch<64, 128, 4, AKM, BKM, EPI>(a, s);
-    case 3: return launch<64, 64, 4, AKM, BKM, EPI>(a, s);
-    // 8 waves (two per SIMD, 64 x 96 each): one 256-CU round for 4096 x {2304, 3072}
-    case 5: return launch<256, 192, 2, AKM, BKM, EPI, 8>(a, s);
-    case 6: return launch<128, 128, 4, AKM, BKM, EPI, 8>(a, s);  // two waves per SIMD (32 x 64 each)
-    case 7: return launch<256, 128, 2, AKM, BKM, EPI, 8>(a, s);
-    // 96 x 96: the [768][3072] / [3072][768] weight gradients are exactly 256 tiles (one per CU) where 128 x 128
-    // leaves 112 CUs idle; 2 x 2 waves of 48 x 48 (3 x 3 MFMA blocks)
-    case 8: return launch<96, 96, 4, AKM, BKM, EPI>(a, s);
-    // 128 x 96: the 4096 x 768 outputs (W_O / W_out forward, dX of QKV / W_O / W_in) are exactly 256 tiles
-    case 9: return launch<128, 96, 4, AKM, BKM, EPI>(a, s);
-    // 96 x 192 / 192 x 96 (2 x 2 waves of 48 x 96 / 96 x 48): the weight gradients with a 2-way reduction split
-    // -- 256 workgroups for [768][3072] / [3072][768], a third fewer operand bytes per CU than 96 x 96
-    case 10: return launch<96, 192, 4, AKM, BKM, EPI>(a, s);
-    case 11: return launch<192, 96, 4, AKM, BKM, EPI>(a, s);
-    // deep LDS rings (5-8 K-tiles, up to 144 KiB): more operand bytes in flight per CU for the intake-bound tiles
-    case 12: return launch<96, 96, 6, AKM, BKM, EPI>(a, s);
-    case 13: return launch<128, 96, 5, AKM, BKM, EPI>(a, s);
-    case 14: return launch<64, 64, 8, AKM, BKM, EPI>(a, s);
-    // 128-deep K-tiles (256-B row segments per DMA, half the K-tiles / barriers per K): the intake experiment
-    case 15: return launch<128, 96, 2, AKM, BKM, EPI, 4, 128>(a, s);
-    case 16: return launch<96, 96, 3, AKM, BKM, EPI, 4, 128>(a, s);
-    case 17: return launch<64, 64, 4, AKM, BKM, EPI, 4, 128>(a, s);
-    case 18: return launch<128, 128, 2, AKM, BKM, EPI, 4, 128>(a, s);
-    // 192 x 192 (2 x 2 waves of 96 x 96, 6 x 6 MFMA blocks): the weight gradients with a 4-way reduction split --
-    // 192 workgroups for [768][3072] / [3072][768] / 144 for [768][2304] at half the operand bytes per flop of
-    // 96 x 96 (the intake-bound regime); 3- and 2-deep rings
-    // (tile 19 was 192 x 192 with a 3-deep ring: wrong results under the reduction split; not offered)
-    // (tile 20 serves mode 3 only: iit_gemm_glds_ok says why)
-    case 20: return launch<192, 192, 2, AKM, BKM, EPI>(a, s);
-    // 192 x 128 / 128 x 192 (2 x 2 waves of 96 x 64 / 64 x 96), 4-deep rings (exactly 160 KiB)
-    case 21: return launch<192, 128, 4, AKM, BKM, EPI>(a, s);
-    case 22: return launch<128, 192, 4, AKM, BKM, EPI>(a, s);
-    // two co-resident workgroups per CU (OCC = 2: <= 80 KiB LDS, <= 256 registers per lane), so one tile's
-    // prologue / epilogue overlaps the other's main loop; shapes with >= 512 tiles
-    case 23: return launch<128, 96, 2, AKM, BKM, EPI, 4, 64, 2>(a, s);
-    case 24: return launch<64, 96, 3, AKM, BKM, EPI, 4, 64, 2>(a, s);
-    case 25: return launch<128, 128, 2, AKM, BKM, EPI, 4, 64, 2>(a, s);
-    case 26: return launch<96, 96, 3, AKM, BKM, EPI, 4, 64, 2>(a, s);
-    case 27: return launch<128, 192, 2, AKM, BKM, EPI, 4, 64, 2>(a, s);
-    case 28: return launch<64, 192, 2, AKM, BKM, EPI, 4, 64, 2>(a, s);
-    // three / four co-resident workgroups per CU: the HBM-bound residual-epilogue shapes ([4096][768] outputs)
-    case 29: return launch<64, 96, 2, AKM, BKM, EPI, 4, 64, 3>(a, s);
-    case 30: return launch<64, 64, 2, AKM, BKM, EPI, 4, 64, 4>(a, s);
-    case 31: return launch<64, 128, 2, AKM, BKM, EPI, 4, 64, 3>(a, s);
-    // the in-flight-depth test on the big 8-wave tiles: 3-deep rings (2 K-tiles in flight while one is consumed,
-    // tile 5 / 7 keep one) within 160 KiB, and the 256 x 256 two-stage tile
-    case 32: return launch<256, 128, 3, AKM, BKM, EPI, 8>(a, s);
-    case 33: return launch<128, 256, 3, AKM, BKM, EPI, 8>(a, s);
-    case 34: return launch<256, 256, 2, AKM, BKM, EPI, 8>(a, s);
-    // (tiles 35-37, 128 / 256 x 288 for the packed-QKV forward -- 8 N-tiles of [*][2304], whole 256-CU rounds --
-    // measured 52.9-53.9 us at M = 8192 vs 39.6 us for tile 27 and 39.0 us hipBLASLt, and the 2-deep 128 x 288
-    // returned NaNs (profiles/qkv_fwd_tiles_r4.txt): removed; not offered)
-    default: return launch<128, 128, 4, AKM, BKM, EPI>(a, s);
+#define X(ID, BM, BN, NS, NW, BK, OCC) \
+  case ID: return launch<BM, BN, NS, AKM, BKM, EPI, NW, BK, OCC>(a, s);
+    IIT_GLDS_TILE_LIST(X)
+#undef X
+    default: return hipErrorInvalidValue;  // unreachable: iit_gemm_glds_ok runs first
   }
+}
+
+// the (layout, epilogue) combinations instantiated for every tile: X(mode, A k-major, B k-major, epilogue)
+#define IIT_GLDS_COMBO_LIST(X)                                                                                   \
+  X(0, false, false, E_BF16) X(0, false, false, E_F32_ACC) X(0, false, false, E_F32_STORE)                       \
+  X(0, false, false, E_DGELU) X(0, false, false, E_DGELU_ERF)                                                    \
+  X(2, false, true, E_BF16) X(2, false, true, E_BF16_BIAS3) X(2, false, true, E_F32_RESID)                       \
+  X(2, false, true, E_GELU) X(2, false, true, E_GELU_ERF) X(2, false, true, E_F32_ACC)                          \
+  X(2, false, true, E_F32_STORE)                                                                                 \
+  X(3, true, true, E_F32_ACC) X(3, true, true, E_F32_STORE)
+
+constexpr bool combo_ok(int mode, int epi) {
+#define X(MODE, AKM, BKM, EPI) \
+  if (mode == (MODE) && epi == (EPI)) return true;
+  IIT_GLDS_COMBO_LIST(X)
+#undef X
+  return false;
 }
 
 }  // namespace
 
-#define IIT_GLDS_TILES 38
-static const int kTileBM[IIT_GLDS_TILES] = {128, 128, 64, 64, 128, 256, 128, 256, 96, 128, 96, 192, 96, 128, 64,
-                                            128, 96, 64, 128, 192, 192, 192, 128, 128, 64, 128, 96, 128, 64,
-                                            64, 64, 64, 256, 128, 256, 128, 256, 128};
-static const int kTileBN[IIT_GLDS_TILES] = {128, 64, 128, 64, 128, 192, 128, 128, 96, 96, 192, 96, 96, 96, 64,
-                                            96, 96, 64, 128, 192, 192, 128, 192, 96, 96, 128, 96, 192, 192,
-                                            96, 64, 128, 128, 256, 256, 288, 288, 288};
-static const int kTileBK[IIT_GLDS_TILES] = {64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64,
-                                            128, 128, 128, 128, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64,
-                                            64, 64, 64, 64, 64, 64, 64, 64, 64};
-
-// 1 when (shape, layout, epilogue, tile) is covered by the LDS-DMA kernel (caller falls back otherwise)
-// tile 40: the 256 x 256 8-phase kernel of gemm_8ph.hip; tiles 41 / 42: the 256 x 256 four-wave 32x32x16 kernel
-// of gemm_4w.hip with 64- / 32-deep K-tiles (2- / 4-slot LDS-DMA rings); no K split for any of them
+// 1 when (shape, layout, epilogue, tile) is covered by the LDS-DMA kernel (caller falls back otherwise); tiles 40-42
+// (gemm_tiles.h: the 256 x 256 kernels of gemm_8ph.hip / gemm_4w.hip) take no K split
 #define IIT_8PH_TILE 40
 #define IIT_4W_TILE 41
 #define IIT_4W32_TILE 42
@@ -145,7 +100,8 @@ IIT_EXPORT int iit_gemm_glds_ok(const void* A, const void* B, const void* C, con
     if (epi == E_BF16_BIAS3 && bias_cols % 8) return 0;
     return 1;
   }
-  if (tile < 0 || tile >= IIT_GLDS_TILES || tile == 19 || tile >= 35) return 0;
+  const TileRow* t = find_tile(kGldsRows, tile);
+  if (!t) return 0;
   // tile 20 (192 x 192, 6 x 6 accumulators per wave) is offered for the weight gradients only: with a k-contiguous A
   // (modes 0 / 2) its kernels need more than 256 VGPRs, and hipcc parks the destinations of the asm-issued
   // ds_read_b128 fragment reads in AGPRs (v_accvgpr_write right after the issue, before the data has landed) and
@@ -155,31 +111,19 @@ IIT_EXPORT int iit_gemm_glds_ok(const void* A, const void* B, const void* C, con
   // atomic split-K: fp32 accumulate only; reduction split-K (``reduce``): fp32 accumulate, store or residual add (the
   // last-arriving split runs the epilogue once on the summed tile)
   const bool split_epi = epi == E_F32_ACC || (reduce && (epi == E_F32_STORE || epi == E_F32_RESID));
-  const int bk = kTileBK[tile];
+  const int bk = t->bk;
   if (splits < 1 || (splits > 1 && (!split_epi || K % (bk * splits)))) return 0;
   if (reduce && splits < 2) return 0;
-  if (!(mode == 0 || mode == 2 || mode == 3)) return 0;
-  const bool epi_ok = mode == 3 ? (epi == E_F32_ACC || epi == E_F32_STORE)
-                                : (epi == E_BF16 || epi == E_BF16_BIAS3 || epi == E_F32_RESID || epi == E_GELU ||
-                                   epi == E_GELU_ERF || epi == E_F32_ACC || epi == E_F32_STORE || epi == E_DGELU ||
-                                   epi == E_DGELU_ERF);
-  if (!epi_ok) return 0;
+  if (!combo_ok(mode, epi)) return 0;
   const bool dg = epi == E_DGELU || epi == E_DGELU_ERF;
-  if (mode == 0 && !(epi == E_BF16 || epi == E_F32_ACC || epi == E_F32_STORE || dg)) return 0;
   if (dg && (mode != 0 || !C2)) return 0;
-  if (M <= 0 || N <= 0 || K <= 0 || M % kTileBM[tile] || N % kTileBN[tile] || K % bk) return 0;
+  if (M <= 0 || N <= 0 || K <= 0 || M % t->bm || N % t->bn || K % bk) return 0;
   if (lda % 8 || ldb % 8 || ldc % 8 || (C2 && ldc2 % 8) || (resid && ldr % 8)) return 0;
   const uintptr_t al = (uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)C2 | (uintptr_t)resid;
   if (al & 15) return 0;
   if (epi == E_BF16_BIAS3 && bias_cols % 8) return 0;
   return 1;
 }
-
-IIT_EXPORT int iit_gemm_glds_sm(const void* A, const void* B, void* C, void* C2, const float* bias0,
-                                const float* bias1, const float* bias2, const float* resid, long lda, long ldb, long ldc,
-                                long ldc2, long ldr, int M, int N, int K, int mode, int epi, int bias_cols, int tile,
-                                int splits, float* csum, float* ws, int* counters, int store_mode, float* bsum,
-                                float* gsq, void* stream);
 
 // the timeline probe of the NEXT iit_gemm_glds* launch from this host thread (scripts/gemm_timeline.py): a
 // [workgroups][64] int64 device buffer, consumed by that launch
@@ -189,15 +133,7 @@ IIT_EXPORT void iit_gemm_glds_set_prof(void* buf) { g_prof_buf = (long long*)buf
 static int g_group_m = 0;
 IIT_EXPORT void iit_gemm_glds_set_group_m(int gm) { g_group_m = gm; }
 
-IIT_EXPORT int iit_gemm_glds(const void* A, const void* B, void* C, void* C2, const float* bias0, const float* bias1,
-                             const float* bias2, const float* resid, long lda, long ldb, long ldc, long ldc2, long ldr,
-                             int M, int N, int K, int mode, int epi, int bias_cols, int tile, int splits,
-                             float* csum, float* ws, int* counters, void* stream) {
-  return iit_gemm_glds_sm(A, B, C, C2, bias0, bias1, bias2, resid, lda, ldb, ldc, ldc2, ldr, M, N, K, mode, epi,
-                          bias_cols, tile, splits, csum, ws, counters, 0, nullptr, nullptr, stream);
-}
-
-// the same with the epilogue store flavour (G2Args::store_mode) and, for the weight gradients (mode 3), the fused
+// the launch, with the epilogue store flavour (G2Args::store_mode) and, for the weight gradients (mode 3), the fused
 // column sums of B (``bsum``, += atomically; nullable); ``gsq`` (fp32 store epilogue, nullable): += the sum of squares
 // of the stored values, spread over 64 slots
 IIT_EXPORT int iit_gemm_glds_sm(const void* A, const void* B, void* C, void* C2, const float* bias0,
@@ -228,22 +164,28 @@ IIT_EXPORT int iit_gemm_glds_sm(const void* A, const void* B, void* C, void* C2,
   if (tile == IIT_8PH_TILE) return iit_gemm_8ph_run(&a, mode, epi, stream);
   if (tile == IIT_4W_TILE) return iit_gemm_4w_run(&a, mode, epi, 64, stream);
   if (tile == IIT_4W32_TILE) return iit_gemm_4w_run(&a, mode, epi, 32, stream);
-#define G2(MODE, AK, BK_, EPI) \
-  if (mode == (MODE) && epi == (EPI)) return (int)launch_tile<AK, BK_, EPI>(a, tile, s);
-  G2(0, false, false, E_BF16)
-  G2(0, false, false, E_F32_ACC)
-  G2(0, false, false, E_F32_STORE)
-  G2(0, false, false, E_DGELU)
-  G2(0, false, false, E_DGELU_ERF)
-  G2(2, false, true, E_BF16)
-  G2(2, false, true, E_BF16_BIAS3)
-  G2(2, false, true, E_F32_RESID)
-  G2(2, false, true, E_GELU)
-  G2(2, false, true, E_GELU_ERF)
-  G2(2, false, true, E_F32_ACC)
-  G2(2, false, true, E_F32_STORE)
-  G2(3, true, true, E_F32_ACC)
-  G2(3, true, true, E_F32_STORE)
-#undef G2
+#define X(MODE, AKM, BKM, EPI) \
+  if (mode == (MODE) && epi == (EPI)) return (int)launch_tile<AKM, BKM, EPI>(a, tile, s);
+  IIT_GLDS_COMBO_LIST(X)
+#undef X
   return (int)hipErrorInvalidValue;
+}
+
+// The tile table of ``family`` (0 glds, 40-42 included; 1 edge; 2 dual dW; 3 dual dX; 4 conv; 5 conv weight
+// gradient) from the lists of gemm_tiles.h: fills up to ``cap`` rows of 8 ints (TileRow) and returns the row count
+// (0: no such family).  Host only; what iit_amd/ops/hip_kernels.py checks its tables against.
+IIT_EXPORT int iit_tile_table(int family, TileRow* out, int cap) {
+  const TileRow* rows = nullptr;
+  int n = 0;
+#define FAMILY(F, ROWS) \
+  if (family == (F)) rows = ROWS, n = (int)(sizeof(ROWS) / sizeof(TileRow));
+  FAMILY(0, kGldsRows)
+  FAMILY(1, kEdgeRows)
+  FAMILY(2, kDualWRows)
+  FAMILY(3, kDualXRows)
+  FAMILY(4, kConvRows)
+  FAMILY(5, kConvWgRows)
+#undef FAMILY
+  for (int i = 0; i < n && i < cap; ++i) out[i] = rows[i];
+  return n;
 }

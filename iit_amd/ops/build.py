@@ -25,7 +25,7 @@ SOURCES = ["gemm.hip", "gemm_glds.hip", "gemm_edge.hip", "gemm_dual.hip", "gemm_
 # avoids the AGPR shuffles hipcc otherwise emits around its register double buffer
 EXTRA_FLAGS = {"gemm_glds.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "gemm_edge.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "conv_nhwc.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "gemm_dual.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "gemm_8ph.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
-HEADERS = ["common.h", "gemm_glds_body.h", "gemm_w4.h", "splice_spec.h", "prefetch.h"]
+HEADERS = ["common.h", "gemm_glds_body.h", "gemm_tiles.h", "gemm_w4.h", "splice_spec.h", "prefetch.h"]
 ARCH = os.environ.get("IIT_OFFLOAD_ARCH", "gfx950")
 
 

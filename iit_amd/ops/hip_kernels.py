@@ -39,7 +39,6 @@ _SIGS = {
     "iit_attn_f32_ok": [c_void_p] * 4 + [c_int] * 4,
     "iit_attn_f32_fwd": [c_void_p] * 6 + [c_int] * 4 + [c_float, c_int, c_void_p],
     "iit_attn_f32_bwd": [c_void_p] * 9 + [c_int] * 4 + [c_float, c_int, c_void_p],
-    "iit_gemm_glds": [c_void_p] * 8 + [c_long] * 5 + [c_int] * 8 + [c_void_p] * 4,
     "iit_gemm_glds_ok": [c_void_p] * 5 + [c_long] * 5 + [c_int] * 9,
     "iit_gemm_glds_sm": [c_void_p] * 8 + [c_long] * 5 + [c_int] * 8 + [c_void_p] * 3 + [c_int] + [c_void_p] * 3,
     "iit_embed_pos_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
@@ -120,21 +119,13 @@ _SIGS = {
                      + [c_int] * 5 + [c_void_p] * 3 + [c_void_p, c_long, c_void_p, c_long, c_int, c_void_p],
     "iit_gemm_glds_set_group_m": [c_int],
     "iit_ioi_hl_label": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    "iit_conv3x3_tiles": [],
-    "iit_conv3x3_ok": [c_long, c_int, c_int, c_int, c_int, c_int, c_int],
-    "iit_conv3x3": [c_void_p] * 4 + [c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                     c_void_p, c_void_p],
-    "iit_conv3x3_rows": [c_int],
+    "iit_tile_table": [c_int, c_void_p, c_int],
     "iit_conv2d_ok": [c_long] + [c_int] * 12,
     "iit_conv2d": [c_void_p] * 4 + [c_long] + [c_int] * 12 + [c_void_p] * 4,
     "iit_conv2d_wgrad_ok": [c_long] + [c_int] * 11,
     "iit_conv2d_wgrad": [c_void_p] * 4 + [c_long] + [c_int] * 12 + [c_void_p] * 3,
     "iit_bn_fwd_tiles": [c_void_p] * 4 + [c_int, c_int] + [c_void_p] * 4 + [c_long, c_int, c_float, c_int, c_void_p,
                                                                            c_float, c_void_p, c_void_p],
-    "iit_conv3x3_wgrad_tiles": [],
-    "iit_conv3x3_wgrad_ok": [c_long, c_int, c_int, c_int, c_int, c_int, c_int],
-    "iit_conv3x3_wgrad": [c_void_p] * 4 + [c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                           c_void_p],
 }
 
 
@@ -149,6 +140,7 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = argtypes
             fn.restype = c_int
+        check_tile_tables(L)  # a Python tile table that has drifted from the library's launches nothing
         _LIB = L
         # XCD-local tile-order group height of the single-problem LDS-DMA launches: 4 M-tiles per column group
         # measured 0.2-0.3 % faster than 8 on the headline step over two alternating rounds on one box (16 slower;
@@ -162,6 +154,37 @@ def lib():
         if dgm:
             L.iit_gemm_dual_set_group_m(int(dgm))
     return _LIB
+
+
+# families of ``iit_tile_table``, in its numbering, and the fields of a row (csrc/gemm_tiles.h TileRow)
+TILE_FAMILIES = ("glds", "edge", "dual_w", "dual_x", "conv", "conv_wgrad")
+TILE_FIELDS = ("bm", "bn", "bk", "ns", "nw", "occ", "aux")
+
+
+def tile_table(family: str, L=None) -> dict:
+    """The library's tile table of ``family``: tile id -> dict of ``TILE_FIELDS`` (host only, no device call)."""
+    L = L or lib()
+    fam = TILE_FAMILIES.index(family)
+    n = L.iit_tile_table(fam, None, 0)
+    buf = (c_int * (8 * n))()
+    L.iit_tile_table(fam, buf, n)
+    return {buf[8 * i]: dict(zip(TILE_FIELDS, buf[8 * i + 1:8 * i + 8])) for i in range(n)}
+
+
+def check_tile_tables(L=None) -> None:
+    """Every tile table of this module against the library's (``lib()`` calls it right after load): the same ids per
+    family and the same (BM, BN) -- for the dual tiles (BM, BN, waves, workgroups per CU) -- for each id.  The tables
+    size buffers that the kernels write by their own BM / BN."""
+    ours = {"glds": GLDS_TILES, "edge": {t: GLDS_TILES.get(t) for t in GLDS_EDGE_TILES}, "conv": CONV_TILES,
+            "conv_wgrad": CONV_WG_TILES, "dual_w": {t: v + DUAL_W_WAVES.get(t, ()) for t, v in DUAL_W_TILES.items()},
+            "dual_x": {t: v + DUAL_X_WAVES.get(t, ()) for t, v in DUAL_X_TILES.items()}}
+    for family, mine in ours.items():
+        theirs = {t: (r["bm"], r["bn"], r["nw"], r["occ"])[:4 if family.startswith("dual") else 2]
+                  for t, r in tile_table(family, L).items()}
+        for t in sorted(set(mine) | set(theirs)):
+            if mine.get(t) != theirs.get(t):
+                raise RuntimeError(f"tile table {family!r}, tile {t}: hip_kernels.py has {mine.get(t)}, the library "
+                                   f"has {theirs.get(t)} (csrc/gemm_tiles.h)")
 
 
 def available() -> bool:
@@ -527,12 +550,13 @@ DUAL_X_TILES = {0: (128, 96), 1: (64, 96), 2: (128, 192), 3: (128, 128),
                 4: (256, 192), 5: (256, 128), 6: (128, 128), 7: (128, 128), 8: (128, 192)}
 
 
-def _dual_family(t: int, first_big: int) -> int:
-    return 2 if t >= 7 else (1 if t >= first_big else 0)
+# (waves, workgroups per CU) of each dual tile: a dW and a dX tile share a launch exactly when these are equal
+DUAL_W_WAVES = {0: (4, 2), 1: (4, 2), 2: (4, 2), 3: (4, 2), 4: (4, 2), 5: (8, 1), 6: (8, 1), 7: (4, 1), 8: (4, 1)}
+DUAL_X_WAVES = {0: (4, 2), 1: (4, 2), 2: (4, 2), 3: (4, 2), 4: (8, 1), 5: (8, 1), 6: (8, 1), 7: (4, 1), 8: (4, 1)}
 
 
 def dual_family_ok(wtile: int, xtile: int) -> bool:
-    return _dual_family(wtile, 5) == _dual_family(xtile, 4)
+    return DUAL_W_WAVES[wtile] == DUAL_X_WAVES[xtile]
 
 
 def _bf16_cuda(*ts) -> bool:
@@ -932,39 +956,12 @@ def zero_page(device) -> torch.Tensor:
     return z
 
 
-def conv3x3_tiles() -> int:
-    return int(lib().iit_conv3x3_tiles())
-
-
-def conv3x3_ok(N: int, H: int, W: int, Cin: int, Cout: int, tile: int, splits: int = 1) -> bool:
-    return bool(lib().iit_conv3x3_ok(N, H, W, Cin, Cout, tile, splits))
-
-
 CONV_TILES = {0: (128, 64), 1: (128, 128), 2: (64, 64), 3: (128, 128), 4: (64, 128), 5: (128, 64)}
 
 
 def conv3x3_rows(tile: int) -> int:
     """Output rows per tile (BM) of forward tile ``tile``: the row-tile size of the ``cstat`` records."""
     return CONV_TILES[tile][0]
-
-
-def conv3x3(x, w, y, N: int, H: int, W: int, Cin: int, Cout: int, flip: bool = False, tile: int = 0,
-            splits: int = 1, cstat=None):
-    """``y`` [N,H,W,Cout] = 3x3 / stride-1 / pad-1 convolution of the NHWC bf16 ``x`` [N,H,W,Cin] with ``w``
-    [Cout,3,3,Cin] (``flip``: the input gradient -- ``x`` = dy [N,H,W,Cout'], ``w`` the forward weight [Cout',3,3,Cin'],
-    output channels ``Cout`` = Cin');
-    ``splits`` > 1: deterministic reduction split over the 9 Cin reduction.  ``cstat`` (fp32, >= 3 Cout T floats,
-    T = N H W / :func:`conv3x3_rows`): per-tile column statistics of ``y`` for :func:`bn_fwd_tiles`."""
-    ws = cnt = None
-    if splits > 1:
-        ws, cnt = split_workspace(N * H * W, Cout, CONV_TILES[tile], splits, x.device)
-    if CHECK_BOUNDS:
-        assert x.numel() >= N * H * W * Cin and y.numel() >= N * H * W * Cout and w.numel() >= 9 * Cin * Cout
-        assert x.dtype == w.dtype == y.dtype == torch.bfloat16
-        if cstat is not None:
-            assert cstat.dtype == torch.float32 and cstat.numel() >= 3 * Cout * (N * H * W // conv3x3_rows(tile))
-    _check(lib().iit_conv3x3(_p(x), _p(w), _p(y), _p(zero_page(x.device)), N, H, W, Cin, Cout, int(flip), tile,
-                             splits, _p(ws), _p(cnt), _p(cstat), _stream()), "conv3x3")
 
 
 def conv2d_ok(N: int, SH: int, SW: int, Cs: int, OH: int, OW: int, Co: int, k: int, s: int, pad: int,
@@ -1024,21 +1021,28 @@ def conv3x3_wgrad_splits(pixels: int) -> list:
     return out
 
 
+# the 3 x 3 / stride-1 / pad-1 convolution (same image size in and out) on the conv2d entry points
+def conv3x3_tiles() -> int:
+    return len(CONV_TILES)
+
+
+def conv3x3_ok(N: int, H: int, W: int, Cin: int, Cout: int, tile: int, splits: int = 1) -> bool:
+    return conv2d_ok(N, H, W, Cin, H, W, Cout, 3, 1, 1, False, tile, splits)
+
+
+def conv3x3(x, w, y, N: int, H: int, W: int, Cin: int, Cout: int, flip: bool = False, tile: int = 0,
+            splits: int = 1, cstat=None):
+    """:func:`conv2d` with ``flip`` as ``transposed`` (the input gradient: ``x`` = dy [N,H,W,Cin], ``w`` the forward
+    weight [Cin,3,3,Cout])."""
+    conv2d(x, w, y, N, H, W, Cin, H, W, Cout, 3, 1, 1, flip, tile, splits, cstat)
+
+
 def conv3x3_wgrad_ok(N: int, H: int, W: int, Cin: int, Cout: int, tile: int, splits: int) -> bool:
-    return bool(lib().iit_conv3x3_wgrad_ok(N, H, W, Cin, Cout, tile, splits))
+    return conv2d_wgrad_ok(N, H, W, Cin, H, W, Cout, 3, 1, 1, tile, splits)
 
 
 def conv3x3_wgrad(dy, x, dw, N: int, H: int, W: int, Cin: int, Cout: int, acc: bool, tile: int, splits: int = 1):
-    """``dw`` [Cout,3,3,Cin] fp32 (+)= the weight gradient of the 3x3 / stride-1 / pad-1 convolution (NHWC bf16 ``dy``
-    [N,H,W,Cout], ``x`` [N,H,W,Cin]); ``splits`` > 1: deterministic reduction split over the pixels."""
-    ws = cnt = None
-    if splits > 1:
-        ws, cnt = split_workspace(Cout, 9 * Cin, CONV_WG_TILES[tile], splits, dy.device)
-    if CHECK_BOUNDS:
-        assert dw.dtype == torch.float32 and dw.numel() >= 9 * Cin * Cout
-        assert dy.numel() >= N * H * W * Cout and x.numel() >= N * H * W * Cin
-    _check(lib().iit_conv3x3_wgrad(_p(dy), _p(x), _p(dw), _p(zero_page(x.device)), N, H, W, Cin, Cout, int(acc), tile,
-                                   splits, _p(ws), _p(cnt), _stream()), "conv3x3_wgrad")
+    conv2d_wgrad(dy, x, dw, N, H, W, Cin, H, W, Cout, 3, 1, 1, acc, tile, splits)
 
 
 def maxpool3s2_bwd(dy, idx, dx, N: int, H: int, W: int, C: int):

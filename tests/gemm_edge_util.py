@@ -9,9 +9,10 @@ last row's ``pad8(extent)`` columns belong to a NaN-filled neighbour inside the 
 import torch
 
 import gemm_exact_util as U
+from iit_amd.ops import hip_kernels as HK
 
 F32, BF16 = torch.float32, torch.bfloat16
-EDGE_TILES = {0: (128, 128), 7: (256, 128), 25: (128, 128)}  # tile id -> (BM, BN); K-tiles of 64
+EDGE_TILES = {t: HK.GLDS_TILES[t] for t in HK.GLDS_EDGE_TILES}  # tile id -> (BM, BN); K-tiles of 64
 BK = 64
 N_REMAINDERS = (1, 7, 8, 9, 81)
 MODE_BKM, MODE_3 = 2, 3

@@ -31,9 +31,10 @@ def K():
 
 
 def test_tiles_match_the_library(K):
-    assert tuple(sorted(E.EDGE_TILES)) == tuple(sorted(K.GLDS_EDGE_TILES))
+    edge = K.tile_table("edge")  # the library's own rows
+    assert tuple(sorted(E.EDGE_TILES)) == tuple(sorted(K.GLDS_EDGE_TILES)) == tuple(sorted(edge))
     for t, (bm, bn) in E.EDGE_TILES.items():
-        assert K.GLDS_TILES[t] == (bm, bn)
+        assert K.GLDS_TILES[t] == (bm, bn) == (edge[t]["bm"], edge[t]["bn"]) and edge[t]["bk"] == E.BK
     assert (E.MODE_BKM, E.MODE_3, E.EPI_BF16, E.EPI_F32_ACC, E.EPI_F32_STORE) == (
         K.MODE_BKM, K.MODE_AKM | K.MODE_BKM, K.EPI_BF16, K.EPI_F32_ACC, K.EPI_F32_STORE)
 
