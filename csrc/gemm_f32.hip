@@ -21,14 +21,18 @@
 //   stores its partial tile (zeros for an empty range) into ws[s][M][N]; a second kernel on the same stream sums
 //   the partials in split order and applies the epilogue.  No atomics, tickets or fences: the kernel boundary orders.
 // * Epilogues, evaluated in the written order: EPI_F32_STORE C = acc (+ bias[n]); EPI_F32_RESID
-//   C = (acc (+ bias[n])) + resid[m][n]; EPI_F32_ACC C = C + acc.
+//   C = (acc (+ bias[n])) + resid[m][n]; EPI_F32_ACC C = C + acc.  Two activation epilogues work with an auxiliary
+//   fp32 matrix aux[M][ldx]: EPI_GELU pre = acc (+ bias[n]), aux = pre, C = gelu_new(pre) (the MLP's W_in forward,
+//   the pre-activation stored in the same pass); EPI_DGELU C = acc * gelu_new'(aux) (dpre out of dY W_out^T; no bias).
+//   gelu_new_f / gelu_new_grad_f of common.h (the sigmoid form).
 // * Workgroup order: the bijective XCD remap of gemm.hip, so the tiles one XCD works on are consecutive (they share
 //   A row panels in that XCD's L2).  It changes which workgroup computes a tile, never what it computes.
 #include "common.h"
 
 namespace {
 
-enum : int { F32_EPI_RESID = 2, F32_EPI_ACC = 5, F32_EPI_STORE = 7 };  // the Epi values of gemm.hip
+// the Epi values of gemm.hip
+enum : int { F32_EPI_RESID = 2, F32_EPI_GELU = 3, F32_EPI_DGELU = 4, F32_EPI_ACC = 5, F32_EPI_STORE = 7 };
 
 struct F32Args {
   const float* A;
@@ -37,7 +41,8 @@ struct F32Args {
   const float* bias;
   const float* resid;
   float* ws;
-  long lda, ldb, ldc, ldr;
+  float* aux;
+  long lda, ldb, ldc, ldr, ldx;
   int M, N, K;
   int k_per_split;
   int splits;
@@ -120,8 +125,16 @@ __device__ __forceinline__ void epilogue_f32(const F32Args& p, int row, int col,
     *dst = *dst + v;
     return;
   }
+  if (p.epi == F32_EPI_DGELU) {
+    *dst = v * gelu_new_grad_f(p.aux[(long)row * p.ldx + col]);
+    return;
+  }
   if (p.bias) v = v + p.bias[col];
   if (p.epi == F32_EPI_RESID) v = v + p.resid[(long)row * p.ldr + col];
+  if (p.epi == F32_EPI_GELU) {
+    p.aux[(long)row * p.ldx + col] = v;
+    v = gelu_new_f(v);
+  }
   *dst = v;
 }
 
@@ -236,34 +249,38 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // tile ids: 0 = 64 x 64 (K-tile 32), 1 = 128 x 128 (K-tile 16).
 // 1 when the kernel covers the problem: fp32 operands whose base pointers are 16-byte aligned (A, B, C, the
-// residual and the split workspace; the bias is read one float at a time and needs 4) and whose leading
-// dimensions are multiples of 4 elements and cover their rows
-IIT_EXPORT int iit_gemm_f32_ok(const void* A, const void* B, const void* C, const void* bias, const void* resid,
-                               const void* ws, long lda, long ldb, long ldc, long ldr, int M, int N, int K, int mode,
-                               int epi, int tile, int splits) {
+// residual, the auxiliary matrix and the split workspace; the bias is read one float at a time and needs 4) and
+// whose leading dimensions are multiples of 4 elements and cover their rows.  ``aux`` [M][ldx] is required by
+// EPI_GELU (written) and EPI_DGELU (read) and ignored by the other epilogues.
+IIT_EXPORT int iit_gemm_f32_aux_ok(const void* A, const void* B, const void* C, const void* bias, const void* resid,
+                                   const void* aux, const void* ws, long lda, long ldb, long ldc, long ldr, long ldx,
+                                   int M, int N, int K, int mode, int epi, int tile, int splits) {
   if (!A || !B || !C || M < 1 || N < 1 || K < 1) return 0;
   if (mode < 0 || mode > 3 || tile < 0 || tile > 1 || splits < 1 || splits > 64) return 0;
-  if (epi != F32_EPI_STORE && epi != F32_EPI_RESID && epi != F32_EPI_ACC) return 0;
+  if (epi != F32_EPI_STORE && epi != F32_EPI_RESID && epi != F32_EPI_ACC && epi != F32_EPI_GELU &&
+      epi != F32_EPI_DGELU)
+    return 0;
   if (!aligned16(A) || !aligned16(B) || !aligned16(C) || ((uintptr_t)bias & 3)) return 0;
   if ((lda & 3) || (ldb & 3) || (ldc & 3)) return 0;
   if (lda < ((mode & 1) ? M : K) || ldb < ((mode & 2) ? N : K) || ldc < N) return 0;
   if (epi == F32_EPI_RESID && (!resid || !aligned16(resid) || (ldr & 3) || ldr < N)) return 0;
-  if (epi == F32_EPI_ACC && bias) return 0;
+  if ((epi == F32_EPI_ACC || epi == F32_EPI_DGELU) && bias) return 0;
+  if ((epi == F32_EPI_GELU || epi == F32_EPI_DGELU) && (!aux || !aligned16(aux) || (ldx & 3) || ldx < N)) return 0;
   if (splits > 1 && (!ws || !aligned16(ws))) return 0;
   return 1;
 }
 
 // launches on ``stream``; no host synchronisation, no allocation.  ``ws``: splits * M * N floats when splits > 1.
-IIT_EXPORT int iit_gemm_f32(const void* A, const void* B, void* C, const float* bias, const float* resid, void* ws,
-                            long lda, long ldb, long ldc, long ldr, int M, int N, int K, int mode, int epi, int tile,
-                            int splits, void* stream) {
-  if (!iit_gemm_f32_ok(A, B, C, bias, resid, ws, lda, ldb, ldc, ldr, M, N, K, mode, epi, tile, splits))
+IIT_EXPORT int iit_gemm_f32_aux(const void* A, const void* B, void* C, const float* bias, const float* resid,
+                                void* aux, void* ws, long lda, long ldb, long ldc, long ldr, long ldx, int M, int N,
+                                int K, int mode, int epi, int tile, int splits, void* stream) {
+  if (!iit_gemm_f32_aux_ok(A, B, C, bias, resid, aux, ws, lda, ldb, ldc, ldr, ldx, M, N, K, mode, epi, tile, splits))
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   F32Args a;
   a.A = (const float*)A; a.B = (const float*)B; a.C = (float*)C;
-  a.bias = bias; a.resid = resid; a.ws = (float*)ws;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = ldr;
+  a.bias = bias; a.resid = resid; a.ws = (float*)ws; a.aux = (float*)aux;
+  a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = ldr; a.ldx = ldx;
   a.M = M; a.N = N; a.K = K;
   a.splits = splits; a.epi = epi;
   const int bk = tile == 1 ? 16 : 32;
@@ -272,4 +289,21 @@ IIT_EXPORT int iit_gemm_f32(const void* A, const void* B, void* C, const float* 
   if (rc != hipSuccess || splits == 1) return (int)rc;
   hipLaunchKernelGGL(gemm_f32_reduce_kernel, dim3(cdiv((long)M * N, 256)), dim3(256), 0, s, a);
   return (int)hipGetLastError();
+}
+
+// the three epilogues without an auxiliary matrix: the exports above with ``aux`` = null
+IIT_EXPORT int iit_gemm_f32_ok(const void* A, const void* B, const void* C, const void* bias, const void* resid,
+                               const void* ws, long lda, long ldb, long ldc, long ldr, int M, int N, int K, int mode,
+                               int epi, int tile, int splits) {
+  if (epi != F32_EPI_STORE && epi != F32_EPI_RESID && epi != F32_EPI_ACC) return 0;
+  return iit_gemm_f32_aux_ok(A, B, C, bias, resid, nullptr, ws, lda, ldb, ldc, ldr, 0, M, N, K, mode, epi, tile,
+                             splits);
+}
+
+IIT_EXPORT int iit_gemm_f32(const void* A, const void* B, void* C, const float* bias, const float* resid, void* ws,
+                            long lda, long ldb, long ldc, long ldr, int M, int N, int K, int mode, int epi, int tile,
+                            int splits, void* stream) {
+  if (epi != F32_EPI_STORE && epi != F32_EPI_RESID && epi != F32_EPI_ACC) return (int)hipErrorInvalidValue;
+  return iit_gemm_f32_aux(A, B, C, bias, resid, nullptr, ws, lda, ldb, ldc, ldr, 0, M, N, K, mode, epi, tile, splits,
+                          stream);
 }

@@ -144,6 +144,12 @@ class LayerNormSite(nn.Module):
             hs = (lambda t: run.site(self.hook_scale, t)) if live else None
             hn = (lambda t: run.site(self.hook_normalized, t)) if live else None
             return TorchOps.rms_norm(run.ops, x, self.w, self.eps, hook_scale=hs, hook_normalized=hn)
+        if getattr(run.ops, "native_layer_norm", False):
+            # hip32n, an unfused backend with an LN kernel (``twin`` and ``prefetch`` do not apply): live hooks go to
+            # the backend too, which then runs TorchOps.layer_norm and counts the fallback
+            hooks = {"hook_scale": lambda t: run.site(self.hook_scale, t),
+                     "hook_normalized": lambda t: run.site(self.hook_normalized, t)} if live else {}
+            return run.ops.layer_norm(x, self.w, self.b, self.eps, **hooks)
         if live or not run.ops.fused:
             return TorchOps.layer_norm(
                 run.ops, x, self.w, self.b, self.eps,

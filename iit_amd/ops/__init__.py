@@ -9,6 +9,10 @@
 * ``hip32x`` – :class:`iit_amd.ops.hip32_ops.HipF32XOps`, ``hip32`` with attention on the
   exact-fp32 MFMA kernel (``csrc/attn_fp32.hip``, S <= 64 and d_head <= 64; the torch op
   otherwise and whenever a score / pattern hook is live).  Opt-in under ``hip32``'s rules.
+* ``hip32n`` – :class:`iit_amd.ops.hip32_ops.HipF32NOps`, ``hip32x`` with the rest of a GPT-2-family
+  block on the repo's kernels when no hook inside the op is live: LayerNorm (``csrc/block_f32.hip``),
+  ``gelu_new`` and its derivative in ``gemm_f32`` epilogues, both residual adds in the projections'
+  epilogues.  Opt-in under ``hip32``'s rules.
 
 ``select_ops(model, backend)`` picks per call: ``backend=None`` means "hip when
 the model lives on a GPU and computes in bf16, else torch".  Asking for ``hip``
@@ -56,11 +60,11 @@ def select_ops(model, backend: Optional[str] = None):
             raise RuntimeError("hip op backend requires the model on a GPU")
         from .hip_ops import get_hip_ops
         return get_hip_ops(model)
-    if backend in ("hip32", "hip32x"):  # opt-in only: ``backend=None`` never selects them
+    if backend in ("hip32", "hip32x", "hip32n"):  # opt-in only: ``backend=None`` never selects them
         if not on_gpu:
             raise RuntimeError(f"{backend} op backend requires the model on a GPU")
-        from .hip32_ops import get_hip32_ops, get_hip32x_ops
-        return (get_hip32_ops if backend == "hip32" else get_hip32x_ops)(model)
+        from .hip32_ops import get_hip32_ops, get_hip32n_ops, get_hip32x_ops
+        return {"hip32": get_hip32_ops, "hip32x": get_hip32x_ops, "hip32n": get_hip32n_ops}[backend](model)
     raise ValueError(f"unknown op backend {backend}")
 
 

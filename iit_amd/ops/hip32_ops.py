@@ -9,6 +9,11 @@ stay where the fp32 torch path has them.  Gradients are returned to autograd exa
 
 ``hip32x`` (:class:`HipF32XOps`) is ``hip32`` plus attention on the exact-fp32 MFMA kernel of
 ``csrc/attn_fp32.hip`` (:class:`AttentionF32Fn`), opt-in in the same way.
+
+``hip32n`` (:class:`HipF32NOps`) is ``hip32x`` plus the rest of a GPT-2-family block: LayerNorm on
+``csrc/block_f32.hip`` (:class:`LayerNormF32Fn`), ``gelu_new`` in the W_in GEMM's epilogue (:class:`MlpInF32Fn`),
+its derivative in the ``dY W_out^T`` GEMM's epilogue (:class:`MlpGeluResidualF32Fn`) and both residual adds in the
+projections' epilogues (``LinearF32Fn``'s ``resid``).  Opt-in in the same way.
 """
 from __future__ import annotations
 
@@ -45,11 +50,11 @@ def _tile(M: int, N: int) -> int:
     return 1 if min(M, N) >= 128 and ((M + 127) // 128) * ((N + 127) // 128) >= K.N_CU else 0
 
 
-def _gemm(A, B, C, M, N, Kd, mode, epi=K.EPI_F32_STORE, bias=None, resid=None):
+def _gemm(A, B, C, M, N, Kd, mode, epi=K.EPI_F32_STORE, bias=None, resid=None, aux=None):
     tile = _tile(M, N)
     K.gemm_f32(A, B, C, M=M, N=N, K=Kd, lda=A.stride(0), ldb=B.stride(0), ldc=C.stride(0), mode=mode, epi=epi,
                bias=bias, resid=resid, ldr=0 if resid is None else resid.stride(0), tile=tile,
-               splits=K.gemm_f32_splits(M, N, Kd, tile))
+               splits=K.gemm_f32_splits(M, N, Kd, tile), aux=aux, ldx=0 if aux is None else aux.stride(0))
 
 
 def _forward(x2, W2, b, r2=None):
@@ -303,6 +308,212 @@ class HipF32XOps(HipF32Ops):
         return TorchOps.attention(self, q, k, v, causal, attn_scale, **kw)
 
 
+def _rows(t: torch.Tensor, d: int) -> torch.Tensor:
+    """``t [..., d]`` as the rows ``[T][d]`` the LayerNorm kernels take: as stored when the last stride is 1 and the
+    row pitch covers the row, else copied once."""
+    t2 = t.reshape(-1, d)
+    if (d == 1 or t2.stride(1) == 1) and (t2.shape[0] == 1 or t2.stride(0) >= d) and t2.dtype == torch.float32:
+        return t2
+    return t2.float().contiguous()
+
+
+class LayerNormF32Fn(torch.autograd.Function):
+    """``y = (x - mean) / sqrt(var + eps) (* w + b)`` over the last dimension of fp32 ``x`` on ``csrc/block_f32.hip``
+    (``d <= 4096``; ``w`` and ``b`` both or neither).  ``x`` and the row statistics are saved; the backward is one
+    ``ln_f32_bwd`` call that returns ``dx``, ``dw`` and ``db`` to autograd (no atomics: the affine gradients are
+    per-block partials added in block order)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, eps: float):
+        d = x.shape[-1]
+        x2 = _rows(x.detach(), d)
+        T = x2.shape[0]
+        y = torch.empty(T, d, dtype=torch.float32, device=x.device)
+        mean = torch.empty(T, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(T, dtype=torch.float32, device=x.device)
+        wd = None if w is None else w.detach()
+        K.ln_f32_fwd(x2, wd, None if b is None else b.detach(), y, mean, rstd, eps)
+        ctx.save_for_backward(x2, mean, rstd, wd)
+        ctx.shape = x.shape
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, mean, rstd, w = ctx.saved_tensors
+        T, d = x2.shape
+        dx = torch.empty(T, d, dtype=torch.float32, device=x2.device)
+        dw = db = None
+        if w is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            dw, db = torch.empty(d, dtype=torch.float32, device=x2.device), torch.empty(
+                d, dtype=torch.float32, device=x2.device)
+        K.ln_f32_bwd(_rows(dy, d), x2, mean, rstd, w, dx, dw, db)
+        need = ctx.needs_input_grad
+        return (dx.view(ctx.shape) if need[0] else None, dw if need[1] else None, db if need[2] else None, None)
+
+
+def _mlp_in_forward(x2, W_in, b_in):
+    """``(pre, post)`` ``[T][d_mlp]`` (contiguous: ``d_mlp % 4 == 0``) of one ``EPI_GELU`` GEMM."""
+    T, Kd = x2.shape
+    N = W_in.shape[1]
+    pre = torch.empty(T, N, dtype=torch.float32, device=x2.device)
+    post = torch.empty(T, N, dtype=torch.float32, device=x2.device)
+    _gemm(x2, W_in, post, T, N, Kd, K.MODE_BKM, K.EPI_GELU, b_in, aux=pre)
+    return pre, post
+
+
+class MlpInF32Fn(torch.autograd.Function):
+    """``post = gelu_new(x @ W_in (+ b_in))``: one GEMM whose epilogue stores the pre-activation beside the result
+    (``d_mlp % 4 == 0``).  ``pre`` is kept for the backward and not returned: ``dpre = dpost * gelu_new'(pre)``
+    (``dgelu_f32``), then ``LinearF32Fn``'s two GEMMs and ``db_in = dpre.sum(0)``."""
+
+    @staticmethod
+    def forward(ctx, x, W_in, b_in):
+        Kd, N = W_in.shape
+        x2 = _operand(x.detach().reshape(-1, Kd))
+        pre, post = _mlp_in_forward(x2, W_in.detach(), None if b_in is None else b_in.detach())
+        ctx.save_for_backward(x2, W_in.detach(), pre)
+        ctx.lead, ctx.has_b = x.shape[:-1], b_in is not None
+        return post.view(*ctx.lead, N)
+
+    @staticmethod
+    def backward(ctx, dpost):
+        x2, W_in, pre = ctx.saved_tensors
+        Kd, N = W_in.shape
+        dpre = torch.empty_like(pre)
+        K.dgelu_f32(dpost.reshape(-1, N).contiguous(), pre, dpre)
+        dx, dw = _backward(x2, W_in, dpre, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        db = dpre.sum(0) if ctx.has_b and ctx.needs_input_grad[2] else None
+        return None if dx is None else dx.view(*ctx.lead, Kd), dw, db
+
+
+class MlpGeluResidualF32Fn(torch.autograd.Function):
+    """``resid + gelu_new(x @ W_in + b_in) @ W_out + b_out``: an ``EPI_GELU`` GEMM and an ``EPI_F32_RESID`` GEMM
+    (``d_mlp % 4 == 0``).  Backward: ``dpre`` out of one ``EPI_DGELU`` GEMM (``dY W_out^T`` with ``aux = pre``),
+    ``dW_out = post^T dY``, ``db_out = dY.sum(0)``, ``dW_in = x^T dpre``, ``db_in = dpre.sum(0)``,
+    ``dx = dpre W_in^T`` and ``dresid = dY``, all returned to autograd."""
+
+    @staticmethod
+    def forward(ctx, x, W_in, b_in, W_out, b_out, resid):
+        d, dm = W_in.shape
+        n_out = W_out.shape[1]
+        x2 = _operand(x.detach().reshape(-1, d))
+        r2 = _operand(resid.detach().reshape(-1, n_out))
+        W_in, W_out = W_in.detach(), W_out.detach()
+        pre, post = _mlp_in_forward(x2, W_in, None if b_in is None else b_in.detach())
+        y = _forward(post, W_out, None if b_out is None else b_out.detach(), r2)
+        ctx.save_for_backward(x2, W_in, W_out, pre, post)
+        ctx.lead, ctx.has_b = x.shape[:-1], (b_in is not None, b_out is not None)
+        return y.view(*resid.shape[:-1], n_out)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, W_in, W_out, pre, post = ctx.saved_tensors
+        d, dm = W_in.shape
+        n_out = W_out.shape[1]
+        T = x2.shape[0]
+        need = ctx.needs_input_grad
+        dy2 = _operand(dy.reshape(-1, n_out))
+        dpre = torch.empty_like(pre)
+        _gemm(dy2, W_out, dpre, T, dm, n_out, K.MODE_NN, K.EPI_DGELU, aux=pre)
+        dw_out = None
+        if need[3]:
+            dw_out = _out(dm, n_out, x2.device)
+            _gemm(post, dy2, dw_out, dm, n_out, T, K.MODE_AKM | K.MODE_BKM)
+        db_out = dy2.sum(0) if ctx.has_b[1] and need[4] else None
+        dx, dw_in = _backward(x2, W_in, dpre, need[0], need[1])
+        db_in = dpre.sum(0) if ctx.has_b[0] and need[2] else None
+        return (None if dx is None else dx.view(*ctx.lead, d), dw_in, db_in, dw_out, db_out,
+                dy if need[5] else None)
+
+
+_GELU_NEW = ("gelu_new", "gelu_fast", "gelu_pytorch_tanh")
+
+
+class HipF32NOps(HipF32XOps):
+    """:class:`HipF32XOps` with the rest of a GPT-2-family block on the repo's kernels when no hook inside the op is
+    live: LayerNorm (``native_layer_norm`` tells ``LayerNormSite.run`` to call ``layer_norm``), ``gelu_new`` and its
+    derivative in GEMM epilogues, the two residual adds in the projections' epilogues (``fuses_residual``).
+    ``calls`` (its own dictionary) also counts ``"layer_norm"`` / ``"layer_norm_fallback"`` and ``"mlp_fused"`` /
+    ``"mlp_fused_fallback"``; the residual projections count under ``"o_proj"`` / ``"mlp_out"``."""
+    name = "hip32n"
+    fused = False
+    native_layer_norm = True
+    fuses_residual = True
+    calls: dict = {}
+
+    def _param(self, p) -> bool:
+        return p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and self.w(p) is p
+
+    def layer_norm(self, x, w, b, eps, **kw):
+        if not kw and K.ln_f32_ok(x) and (w is None) == (b is None) and (
+                w is None or (self._param(w) and self._param(b) and w.shape == b.shape == x.shape[-1:])):
+            self._count("layer_norm")
+            return LayerNormF32Fn.apply(x, w, b, eps)
+        self._count("layer_norm_fallback")
+        return TorchOps.layer_norm(self, x, w, b, eps, **kw)
+
+    def _lin_resid(self, op: str, x, W, b, resid):
+        """``resid + x @ W (+ b)`` by ``LinearF32Fn``'s residual epilogue under the conditions of ``_lin``; None when
+        they do not hold (the caller composes the fallback, which counts itself)."""
+        Wv = self.w(W)
+        bv = None if b is None else self.w(b)
+        if not (Wv.dim() == 2 and x.dtype == torch.float32 and x.is_cuda and x.numel() > 0
+                and resid.dtype == torch.float32 and resid.is_cuda and resid.shape[:-1] == x.shape[:-1]
+                and resid.shape[-1] == Wv.shape[1]
+                and (bv is None or (bv.dim() == 1 and bv.dtype == torch.float32 and bv.is_contiguous()))):
+            return None
+        if not weight_ok(_operand(x.detach().reshape(-1, x.shape[-1])), Wv):
+            return None
+        self._count(op)
+        return LinearF32Fn.apply(x, Wv, bv, resid)
+
+    def o_proj_residual(self, z, W_O, b_O, resid):
+        Wv = self.w(W_O)
+        if Wv.dim() == 3 and Wv.is_contiguous():
+            H, dh, d = Wv.shape
+            out = self._lin_resid("o_proj", z.reshape(*z.shape[:-2], H * dh), Wv.view(H * dh, d), b_O, resid)
+            if out is not None:
+                return out
+        return self.residual(resid, self.o_proj(z, W_O, b_O))
+
+    def mlp_out_residual(self, post, W_out, b_out, resid):
+        out = self._lin_resid("mlp_out", post, W_out, b_out, resid)
+        return out if out is not None else self.residual(resid, self.mlp_out(post, W_out, b_out))
+
+    def _mlp_in_ok(self, x, W_in, b_in) -> bool:
+        if not (x.is_cuda and x.dtype == torch.float32 and x.numel() > 0 and W_in.dim() == 2 and W_in.shape[1] % 4 == 0
+                and self.w(W_in) is W_in and (b_in is None or (b_in.dim() == 1 and self._param(b_in)))):
+            return False
+        return weight_ok(_operand(x.detach().reshape(-1, x.shape[-1])), W_in)
+
+    def mlp_in(self, x, W_in, b_in, act: str, hook_pre=None):
+        """With no ``hook_pre`` and an act of the ``gelu_new`` family (``d_mlp % 4 == 0``): :class:`MlpInF32Fn`, and
+        ``(None, post)`` is returned -- every caller that passes no ``hook_pre`` discards the first element, and
+        the pre-activation stays inside the function for its backward.  Anything else: the inherited method."""
+        if hook_pre is None and act in _GELU_NEW and self._mlp_in_ok(x, W_in, b_in):
+            self._count("mlp_in")
+            return None, MlpInF32Fn.apply(x, W_in, b_in)
+        return super().mlp_in(x, W_in, b_in, act, hook_pre=hook_pre)
+
+    def mlp_gelu_residual(self, x, W_in, b_in, W_out, b_out, resid):
+        """The whole ``gelu_new`` MLP and its residual add (:class:`MlpGeluResidualF32Fn`) when both weights pass
+        ``weight_ok``; else ``mlp_in`` and ``mlp_out_residual`` composed."""
+        if self._mlp_in_ok(x, W_in, b_in) and W_out.dim() == 2 and self.w(W_out) is W_out and W_out.is_cuda \
+                and W_out.dtype == torch.float32 and (b_out is None or (b_out.dim() == 1 and self._param(b_out))) \
+                and resid.is_cuda and resid.dtype == torch.float32 and resid.shape[:-1] == x.shape[:-1] \
+                and resid.shape[-1] == W_out.shape[1]:
+            # post is allocated aligned and contiguous [T][d_mlp]: W_out itself stands in for it and for the output
+            if W_out.stride(1) == 1 and W_out.shape[0] == W_in.shape[1] and K.gemm_f32_ok(
+                    W_out, W_out, W_out, M=x.numel() // x.shape[-1], N=W_out.shape[1], K=W_in.shape[1],
+                    lda=W_in.shape[1], ldb=W_out.stride(0), ldc=_up4(W_out.shape[1]), mode=K.MODE_BKM,
+                    epi=K.EPI_F32_STORE):
+                self._count("mlp_fused")
+                return MlpGeluResidualF32Fn.apply(x, W_in, b_in, W_out, b_out, resid)
+        self._count("mlp_fused_fallback")
+        _, post = self.mlp_in(x, W_in, b_in, "gelu_new")
+        return self.mlp_out_residual(post, W_out, b_out, resid)
+
+
 _OPS = {}
 
 
@@ -323,3 +534,8 @@ def get_hip32_ops(model) -> HipF32Ops:
 def get_hip32x_ops(model) -> HipF32XOps:
     """``hip32x`` under the same rules as :func:`get_hip32_ops`."""
     return _get(HipF32XOps, model)
+
+
+def get_hip32n_ops(model) -> HipF32NOps:
+    """``hip32n`` under the same rules as :func:`get_hip32_ops`."""
+    return _get(HipF32NOps, model)

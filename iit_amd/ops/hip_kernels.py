@@ -34,6 +34,15 @@ _SIGS = {
     "iit_gemm": [c_void_p] * 10 + [c_long] * 5 + [c_int] * 12 + [c_void_p],
     "iit_gemm_f32": [c_void_p] * 6 + [c_long] * 4 + [c_int] * 7 + [c_void_p],
     "iit_gemm_f32_ok": [c_void_p] * 6 + [c_long] * 4 + [c_int] * 7,
+    "iit_gemm_f32_aux": [c_void_p] * 7 + [c_long] * 5 + [c_int] * 7 + [c_void_p],
+    "iit_gemm_f32_aux_ok": [c_void_p] * 7 + [c_long] * 5 + [c_int] * 7,
+    "iit_ln_f32_part_rows": [],
+    "iit_ln_f32_fwd_ok": [c_void_p] * 6 + [c_int, c_int, c_long, c_long],
+    "iit_ln_f32_fwd": [c_void_p] * 6 + [c_int, c_int, c_long, c_long, c_float, c_void_p],
+    "iit_ln_f32_bwd_ok": [c_void_p] * 9 + [c_int, c_int, c_long, c_long, c_long],
+    "iit_ln_f32_bwd": [c_void_p] * 9 + [c_int, c_int, c_long, c_long, c_long, c_void_p],
+    "iit_dgelu_f32_ok": [c_void_p] * 3 + [c_long],
+    "iit_dgelu_f32": [c_void_p] * 3 + [c_long, c_void_p],
     "iit_attn_f32_lds": [c_int] * 3,
     "iit_attn_f32_waves": [c_int] * 3,
     "iit_attn_f32_ok": [c_void_p] * 4 + [c_int] * 4,
@@ -418,16 +427,18 @@ def _f32_cuda(*ts) -> bool:
     return all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in ts)
 
 
-def gemm_f32_ok(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, bias=None, resid=None, ldr=0, tile=0, splits=1) -> bool:
+def gemm_f32_ok(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, bias=None, resid=None, ldr=0, tile=0, splits=1,
+                aux=None, ldx=0) -> bool:
     """Whether the fp32 MFMA kernel covers this problem: fp32 GPU operands, 16-byte aligned base pointers, leading
-    dimensions that are multiples of 4 elements, ``mode`` 0..3, ``EPI_F32_STORE`` / ``_RESID`` / ``_ACC``, a tile of
-    ``GEMM_F32_TILES`` and 1..64 splits."""
-    if not _f32_cuda(A, B, C, bias, resid) or tile not in GEMM_F32_TILES:
+    dimensions that are multiples of 4 elements, ``mode`` 0..3, ``EPI_F32_STORE`` / ``_RESID`` / ``_ACC`` or -- with
+    the auxiliary matrix ``aux [M][ldx]`` -- ``EPI_GELU`` / ``EPI_DGELU``, a tile of ``GEMM_F32_TILES`` and 1..64
+    splits."""
+    if not _f32_cuda(A, B, C, bias, resid, aux) or tile not in GEMM_F32_TILES:
         return False
     # the split workspace comes from torch's allocator (512-byte aligned): a stand-in aligned address
     ws = 16 if splits > 1 else None
-    return bool(lib().iit_gemm_f32_ok(_p(A), _p(B), _p(C), _p(bias), _p(resid), ws, lda, ldb, ldc, ldr, M, N, K, mode,
-                                      epi, tile, splits))
+    return bool(lib().iit_gemm_f32_aux_ok(_p(A), _p(B), _p(C), _p(bias), _p(resid), _p(aux), ws, lda, ldb, ldc, ldr,
+                                          ldx, M, N, K, mode, epi, tile, splits))
 
 
 def gemm_f32_splits(M: int, N: int, K: int, tile: int = 0) -> int:
@@ -439,23 +450,114 @@ def gemm_f32_splits(M: int, N: int, K: int, tile: int = 0) -> int:
     return max(1, min(N_CU // tiles, K // 128, 64))
 
 
-def gemm_f32(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, bias=None, resid=None, ldr=0, tile=0, splits=1):
+def gemm_f32(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, bias=None, resid=None, ldr=0, tile=0, splits=1, aux=None,
+             ldx=0):
     """C = A @ B (+ epilogue) in exact fp32 on ``v_mfma_f32_16x16x4_f32`` (``csrc/gemm_f32.hip``); fp32 operands in
-    the layout of ``mode`` (``MODE_AKM`` / ``MODE_BKM`` bits), strides in elements.  ``splits > 1``: deterministic
-    split-K through a ``[splits][M][N]`` workspace allocated here with ``torch.empty`` (the caching allocator keeps
-    it alive for a capturing graph's pool, so the call is safe under ``torch.cuda.graph``).  Raises, without
-    launching, for a problem ``gemm_f32_ok`` refuses."""
+    the layout of ``mode`` (``MODE_AKM`` / ``MODE_BKM`` bits), strides in elements.  ``aux [M][ldx]``: the
+    pre-activation that ``EPI_GELU`` stores beside ``C = gelu_new(pre)`` and ``EPI_DGELU`` reads
+    (``C = acc * gelu_new'(aux)``).  ``splits > 1``: deterministic split-K through a ``[splits][M][N]`` workspace
+    allocated here with ``torch.empty`` (the caching allocator keeps it alive for a capturing graph's pool, so the
+    call is safe under ``torch.cuda.graph``).  Raises, without launching, for a problem ``gemm_f32_ok`` refuses."""
     if not gemm_f32_ok(A, B, C, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, mode=mode, epi=epi, bias=bias, resid=resid,
-                       ldr=ldr, tile=tile, splits=splits):
+                       ldr=ldr, tile=tile, splits=splits, aux=aux, ldx=ldx):
         raise RuntimeError(f"iit_gemm_f32: unsupported problem M={M} N={N} K={K} lda={lda} ldb={ldb} ldc={ldc} "
-                           f"ldr={ldr} mode={mode} epi={epi} tile={tile} splits={splits} (fp32 GPU operands, 16-byte "
-                           f"aligned pointers, leading dimensions multiples of 4)")
+                           f"ldr={ldr} ldx={ldx} mode={mode} epi={epi} tile={tile} splits={splits} (fp32 GPU operands, "
+                           f"16-byte aligned pointers, leading dimensions multiples of 4)")
     if CHECK_BOUNDS:
         _gemm_bounds("iit_gemm_f32", A, B, C, None, resid, M, N, K, lda, ldb, ldc, 0, ldr, mode)
         _bounds("iit_gemm_f32", ("bias", bias, 1, N, N))
+        if epi in (EPI_GELU, EPI_DGELU):
+            _bounds("iit_gemm_f32", ("aux", aux, M, N, ldx))
     ws = torch.empty(splits * M * N, dtype=torch.float32, device=A.device) if splits > 1 else None
-    _check(lib().iit_gemm_f32(_p(A), _p(B), _p(C), _p(bias), _p(resid), _p(ws), lda, ldb, ldc, ldr, M, N, K, mode, epi,
-                              tile, splits, _stream()), "iit_gemm_f32")
+    _check(lib().iit_gemm_f32_aux(_p(A), _p(B), _p(C), _p(bias), _p(resid), _p(aux), _p(ws), lda, ldb, ldc, ldr, ldx,
+                                  M, N, K, mode, epi, tile, splits, _stream()), "iit_gemm_f32")
+
+
+# ------------------------------------------------------------------------------ fp32 block glue (csrc/block_f32.hip)
+LN_F32_MAX_D = 4096
+
+
+def _rows_f32(what: str, **ts):
+    """The named ``[T][d]`` operands as ``(T, d, pitches)``: fp32 GPU tensors of one shape with unit column stride
+    and a row pitch that covers the row (a single row may carry any pitch: ``d`` is passed)."""
+    shape = None
+    lds = []
+    for name, t in ts.items():
+        if not (isinstance(t, torch.Tensor) and t.dim() == 2 and t.is_cuda and t.dtype == torch.float32):
+            raise ValueError(f"{what}: {name} must be a 2-D fp32 GPU tensor")
+        shape = shape or tuple(t.shape)
+        if tuple(t.shape) != shape or min(shape) < 1:
+            raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected non-empty {shape}")
+        T, d = shape
+        ld = d if T == 1 else t.stride(0)
+        if (d > 1 and t.stride(1) != 1) or ld < d:
+            raise ValueError(f"{what}: {name} needs unit column stride and a row pitch >= {d}, got {t.stride()}")
+        lds.append(ld)
+    return shape[0], shape[1], lds
+
+
+def _vec_f32(what: str, n: int, **ts):
+    for name, t in ts.items():
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+            raise ValueError(f"{what}: {name} must be {n} contiguous fp32 values on the GPU")
+
+
+def ln_f32_ok(x: torch.Tensor, w=None, b=None) -> bool:
+    """Whether ``csrc/block_f32.hip`` normalises the last dimension of ``x``: fp32 on the GPU, ``1 <= d <= 4096``,
+    at least one row; ``w`` and ``b`` both or neither, contiguous fp32 ``[d]`` on the GPU."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() >= 1 and x.numel() > 0
+            and x.shape[-1] <= LN_F32_MAX_D and (w is None) == (b is None)):
+        return False
+    return all(p is None or (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+                             and tuple(p.shape) == (x.shape[-1],)) for p in (w, b))
+
+
+def ln_f32_part_rows() -> int:
+    """Rows that one block of ``iit_ln_f32_bwd`` covers (one ``[2][d]`` partial per block)."""
+    return int(lib().iit_ln_f32_part_rows())
+
+
+def ln_f32_fwd(x, w, b, y, mean, rstd, eps: float):
+    """``y = (x - mean) * rstd (* w + b)`` over fp32 rows ``x``, ``y`` ``[T][d]`` (their own row pitches), with the
+    row statistics stored to ``mean`` / ``rstd`` ``[T]`` (``csrc/block_f32.hip``; ``w`` and ``b`` both or neither).
+    Launches on the current stream; raises ``ValueError``, without launching, for what the kernel does not take."""
+    T, d, (ldx, ldy) = _rows_f32("ln_f32_fwd", x=x, y=y)
+    _vec_f32("ln_f32_fwd", d, w=w, b=b)
+    _vec_f32("ln_f32_fwd", T, mean=mean, rstd=rstd)
+    if not lib().iit_ln_f32_fwd_ok(_p(x), _p(w), _p(b), _p(y), _p(mean), _p(rstd), T, d, ldx, ldy):
+        raise ValueError(f"ln_f32_fwd: iit_ln_f32_fwd_ok refuses T={T} d={d} ldx={ldx} ldy={ldy}")
+    if CHECK_BOUNDS:
+        _bounds("iit_ln_f32_fwd", ("x", x, T, d, ldx), ("y", y, T, d, ldy))
+    _check(lib().iit_ln_f32_fwd(_p(x), _p(w), _p(b), _p(y), _p(mean), _p(rstd), T, d, ldx, ldy, eps, _stream()),
+           "iit_ln_f32_fwd")
+
+
+def ln_f32_bwd(dy, x, mean, rstd, w, dx, dw=None, db=None):
+    """``dx`` of :func:`ln_f32_fwd` and, with ``dw`` and ``db`` given, the affine gradients ``sum_rows dy * xhat`` and
+    ``sum_rows dy`` (stored, not accumulated): per-block partials in a ``[blocks][2][d]`` workspace allocated here
+    with ``torch.empty`` (safe under graph capture, like ``gemm_f32``'s), added in block order by a second kernel."""
+    T, d, (lddy, ldx, lddx) = _rows_f32("ln_f32_bwd", dy=dy, x=x, dx=dx)
+    _vec_f32("ln_f32_bwd", d, w=w, dw=dw, db=db)
+    _vec_f32("ln_f32_bwd", T, mean=mean, rstd=rstd)
+    part = None
+    if dw is not None:
+        part = torch.empty(-(-T // ln_f32_part_rows()) * 2 * d, dtype=torch.float32, device=x.device)
+    if not lib().iit_ln_f32_bwd_ok(_p(dy), _p(x), _p(mean), _p(rstd), _p(w), _p(dx), _p(part), _p(dw), _p(db), T, d,
+                                   ldx, lddy, lddx):
+        raise ValueError(f"ln_f32_bwd: iit_ln_f32_bwd_ok refuses T={T} d={d} (dw and db both or neither, with w)")
+    if CHECK_BOUNDS:
+        _bounds("iit_ln_f32_bwd", ("dy", dy, T, d, lddy), ("x", x, T, d, ldx), ("dx", dx, T, d, lddx))
+    _check(lib().iit_ln_f32_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _p(w), _p(dx), _p(part), _p(dw), _p(db), T, d, ldx,
+                                lddy, lddx, _stream()), "iit_ln_f32_bwd")
+
+
+def dgelu_f32(dpost, pre, dpre):
+    """``dpre = dpost * gelu_new'(pre)`` over contiguous fp32 tensors of one size (``csrc/block_f32.hip``)."""
+    n = pre.numel()
+    _vec_f32("dgelu_f32", n, dpost=dpost, pre=pre, dpre=dpre)
+    if not lib().iit_dgelu_f32_ok(_p(dpost), _p(pre), _p(dpre), n):
+        raise ValueError(f"dgelu_f32: iit_dgelu_f32_ok refuses n={n}")
+    _check(lib().iit_dgelu_f32(_p(dpost), _p(pre), _p(dpre), n, _stream()), "iit_dgelu_f32")
 
 
 # ------------------------------------------------------------------------------ fp32 attention (csrc/attn_fp32.hip)

@@ -69,6 +69,7 @@ def measure(fns: dict, leaves, do, causal: bool, scale: float, inner: int, round
     ``inner`` calls timed with device events, else eagerly under ``perf_counter``."""
     cuda = do.is_cuda
     runs = {}
+    keep = []  # every graph's leaves: a graph reads them at their addresses, so they live as long as the graphs do
     for name, fn in fns.items():
         if not cuda:
             out = step(fn, leaves, do, causal, scale)
@@ -79,6 +80,7 @@ def measure(fns: dict, leaves, do, causal: bool, scale: float, inner: int, round
         # AccumulateGrad node kept alive from an earlier use on the default stream "may ... break CUDA graph capture";
         # a capture through such leaves did not survive here, and that warning is the supposed, not a proven, reason
         lv = [t.detach().clone().requires_grad_() for t in leaves]
+        keep.append(lv)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):  # warm-up outside capture

@@ -11,6 +11,7 @@ epochs run, the wall-clock, whether the early-stop criterion was met, and the fi
     python scripts/time_to_iia.py --model gpt2-small --dtype bf16 --epochs 20
     python scripts/time_to_iia.py --model ioi-6l --fp32-backend hip32 --epochs 30   # projections on csrc/gemm_f32.hip
     python scripts/time_to_iia.py --model ioi-6l --fp32-backend hip32x --epochs 30  # + attention on csrc/attn_fp32.hip
+    python scripts/time_to_iia.py --model ioi-6l --fp32-backend hip32n --epochs 30  # + LayerNorm, fused GELU MLP
 """
 from __future__ import annotations
 
@@ -39,7 +40,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--graphs", type=int, default=1, help="1: engine default, 2: force graphs, 0: eager")
     ap.add_argument("--seed", type=int, default=0, help="torch / numpy seed (the reference uses 0)")
-    ap.add_argument("--fp32-backend", default="torch", choices=["torch", "hip32", "hip32x"],
+    ap.add_argument("--fp32-backend", default="torch", choices=["torch", "hip32", "hip32x", "hip32n"],
                     help="op backend of an fp32 native run, as train_ioi.py --fp32-backend")
     ap.add_argument("--dump-epochs", default=None, help="write every epoch's (epoch, wall s, metrics) as JSON lines")
     args = ap.parse_args()
@@ -60,7 +61,7 @@ def main():
         cfg.update(ioi_cfg)
     cfg.update(init_weights=True, device=str(dev), dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     ll = HookedTransformer(cfg)
-    if args.dtype == "fp32" and args.engine == "native" and args.fp32_backend in ("hip32", "hip32x"):
+    if args.dtype == "fp32" and args.engine == "native" and args.fp32_backend in ("hip32", "hip32x", "hip32n"):
         ll.set_op_backend(args.fp32_backend)
     elif args.dtype == "fp32" or args.engine == "reference":
         ll.set_op_backend("torch")
