@@ -22,7 +22,14 @@
 // * The backward recomputes P = exp2((s - lse) log2 e), forms D = rowsum(P o dP) (z is not needed) and
 //   dS = P (dP - D) scale.  A causal product skips the key tiles above the diagonal.
 // * No atomics; every sum has one fixed order, so results are bit-identical from run to run.
+// * The paired forward (iit_attn_f32_fwd_pair) is the forward over 2B batches, rows [0, B) base and [B, 2B) source,
+//   with an interchange splice of z in the store: a SpliceSpec (splice_spec.h) over the base shape [B][S][H][dh]
+//   selects the elements of a base row that the source wave of the same (batch, head) stores, and the base wave
+//   stores the others; the two never write the same element.  The masked backward (iit_attn_f32_bwd_masked) stages
+//   the selected elements of dO as +0.  Both are the plain kernels' second template instantiation; the plain
+//   instantiation takes an empty trailing argument and compiles to the same instructions as without it.
 #include "common.h"
+#include "splice_spec.h"
 
 namespace {
 
@@ -42,6 +49,14 @@ struct AttnF32Args {
   int causal;
   int waves;
 };
+
+// the trailing kernel argument: the spec of the paired forward / masked backward, nothing for the plain kernels
+template <bool WITH>
+struct SpecArg {
+  SpliceSpec sp;
+};
+template <>
+struct SpecArg<false> {};
 
 inline int up16(int n) { return (n + 15) / 16 * 16; }
 
@@ -101,6 +116,62 @@ __device__ __forceinline__ void store4(float* base, long ss, bool vec, int row, 
   }
 }
 
+// bit r set iff element (c0, c1, c2, d + r) is selected, for the chunk's elements below dh: dimensions 0..2 once per
+// chunk, dimension 3 per element
+__device__ __forceinline__ int sel4(const SpliceSpec& sp, int c0, int c1, int c2, int d, int dh) {
+  if (!(in_ranges(sp, 0, c0) && in_ranges(sp, 1, c1) && in_ranges(sp, 2, c2))) return 0;
+  int bits = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (d + r < dh && in_ranges(sp, 3, d + r)) bits |= 1 << r;
+  return bits;
+}
+
+// store4 of the elements whose bit is set: a whole chunk as one 16-byte store on the vector path, a partial one
+// element by element, none at all for bits == 0
+__device__ __forceinline__ void store4_bits(float* base, long ss, bool vec, int row, int d, int dh, f32x4 v, int bits) {
+  if (d >= dh || bits == 0) return;
+  float* p = base + (long)row * ss + d;
+  if (vec && bits == 15) {
+    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (d + r < dh && ((bits >> r) & 1)) p[r] = v[r];
+  }
+}
+
+// stage() of one head's dO rows with the selected elements replaced by +0 (a selection, never a product: a NaN
+// there does not reach LDS); a wholly selected chunk is not loaded
+__device__ __forceinline__ void stage_masked(const float* base, long ss, bool vec, bool active, int S, int dh, int Sp,
+                                             int Dp, float* lds, int lane, const SpliceSpec& sp, int b, int h) {
+  const int per_row = Dp >> 2, DP = Dp + 2;
+  for (int c = lane; c < Sp * per_row; c += 64) {
+    const int row = c / per_row, col = (c % per_row) * 4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (active && row < S && col < dh) {
+      const float* p = base + (long)row * ss + col;
+      const int n = dh - col;
+      const int sel = sel4(sp, b, row, h, col, dh);
+      if (vec) {
+        if (sel != 15) v = *(const float4*)p;
+      } else {
+        if (!(sel & 1)) v.x = p[0];
+        if (n > 1 && !(sel & 2)) v.y = p[1];
+        if (n > 2 && !(sel & 4)) v.z = p[2];
+        if (n > 3 && !(sel & 8)) v.w = p[3];
+      }
+      v.x = (sel & 1) ? 0.f : v.x;
+      v.y = (sel & 2) ? 0.f : v.y;
+      v.z = (sel & 4) ? 0.f : v.z;
+      v.w = (sel & 8) ? 0.f : v.w;
+    }
+    float* d = lds + row * DP + col;
+    *(float2*)d = make_float2(v.x, v.y);
+    *(float2*)(d + 2) = make_float2(v.z, v.w);
+  }
+}
+
 // butterfly over the 16 lanes that hold one score row; every lane ends with the same bits
 __device__ __forceinline__ float row_max16(float v) {
 #pragma unroll
@@ -117,7 +188,11 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-__global__ __launch_bounds__(256) void attn_f32_fwd_kernel(AttnF32Args p) {
+// PAIR: rows [0, B) of the 2B batches are base and rows [B, 2B) source; ``sp`` selects, over the base shape
+// [B][S][H][dh], the elements of a base row's z that the source wave of the same (batch - B, head) writes instead of
+// the base wave (disjoint elements: no ordering between the two waves is needed)
+template <bool PAIR>
+__global__ __launch_bounds__(256) void attn_f32_fwd_kernel(AttnF32Args p, SpecArg<PAIR> x) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, c = lane & 15;
@@ -201,12 +276,27 @@ __global__ __launch_bounds__(256) void attn_f32_fwd_kernel(AttnF32Args p) {
       for (int kb = 0; kb < kend; kb += 4) acc = mfma4(va[kb * DP], pb[kb], acc);
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[r] = acc[r] * inv;
-      if (active && i < S) store4(z, p.sz.s, vz, i, td * 16 + 4 * g, dh, acc);
+      if constexpr (!PAIR) {
+        if (active && i < S) store4(z, p.sz.s, vz, i, td * 16 + 4 * g, dh, acc);
+      } else if (active && i < S) {
+        const int d = td * 16 + 4 * g;
+        const int nb = p.B >> 1;
+        const bool source = b >= nb;
+        const int sel = sel4(x.sp, (int)(source ? b - nb : b), i, (int)h, d, dh);  // per valid element of the chunk
+        if (source) {
+          store4(z, p.sz.s, vz, i, d, dh, acc);
+          store4_bits(z - (long)nb * p.sz.b, p.sz.s, vz, i, d, dh, acc, sel);
+        } else {
+          store4_bits(z, p.sz.s, vz, i, d, dh, acc, ~sel & 15);
+        }
+      }
     }
   }
 }
 
-__global__ __launch_bounds__(256) void attn_f32_bwd_kernel(AttnF32Args p) {
+// MASKED: the elements of dO that ``sp`` selects (over [B][S][H][dh]) are staged as +0
+template <bool MASKED>
+__global__ __launch_bounds__(256) void attn_f32_bwd_kernel(AttnF32Args p, SpecArg<MASKED> x) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, c = lane & 15;
@@ -227,7 +317,11 @@ __global__ __launch_bounds__(256) void attn_f32_bwd_kernel(AttnF32Args p) {
   stage(p.q + b * p.sq.b + h * p.sq.h, p.sq.s, vec4_ok(p.q, p.sq, dh), active, S, dh, Sp, Dp, Qs, lane);
   stage(p.k + b * p.sk.b + h * p.sk.h, p.sk.s, vec4_ok(p.k, p.sk, dh), active, S, dh, Sp, Dp, Ks, lane);
   stage(p.v + b * p.sv.b + h * p.sv.h, p.sv.s, vec4_ok(p.v, p.sv, dh), active, S, dh, Sp, Dp, Vs, lane);
-  stage(p.dout + b * p.sdo.b + h * p.sdo.h, p.sdo.s, vec4_ok(p.dout, p.sdo, dh), active, S, dh, Sp, Dp, Os, lane);
+  if constexpr (MASKED)
+    stage_masked(p.dout + b * p.sdo.b + h * p.sdo.h, p.sdo.s, vec4_ok(p.dout, p.sdo, dh), active, S, dh, Sp, Dp, Os,
+                 lane, x.sp, (int)b, (int)h);
+  else
+    stage(p.dout + b * p.sdo.b + h * p.sdo.h, p.sdo.s, vec4_ok(p.dout, p.sdo, dh), active, S, dh, Sp, Dp, Os, lane);
   __syncthreads();
 
   const int nt = Sp >> 4;
@@ -347,8 +441,8 @@ IIT_EXPORT int iit_attn_f32_fwd(const void* q, const void* k, const void* v, voi
   a.scale = scale; a.causal = causal;
   a.waves = waves_for(S, dh, false);
   const size_t lds = a.waves * wave_floats(S, dh, false) * sizeof(float);
-  hipLaunchKernelGGL(attn_f32_fwd_kernel, dim3(cdiv((long)B * H, a.waves)), dim3(64 * a.waves), lds,
-                     (hipStream_t)stream, a);
+  hipLaunchKernelGGL(attn_f32_fwd_kernel<false>, dim3(cdiv((long)B * H, a.waves)), dim3(64 * a.waves), lds,
+                     (hipStream_t)stream, a, SpecArg<false>{});
   return (int)hipGetLastError();
 }
 
@@ -369,7 +463,71 @@ IIT_EXPORT int iit_attn_f32_bwd(const void* q, const void* k, const void* v, con
   a.scale = scale; a.causal = causal;
   a.waves = waves_for(S, dh, true);
   const size_t lds = a.waves * wave_floats(S, dh, true) * sizeof(float);
-  hipLaunchKernelGGL(attn_f32_bwd_kernel, dim3(cdiv((long)B * H, a.waves)), dim3(64 * a.waves), lds,
-                     (hipStream_t)stream, a);
+  hipLaunchKernelGGL(attn_f32_bwd_kernel<false>, dim3(cdiv((long)B * H, a.waves)), dim3(64 * a.waves), lds,
+                     (hipStream_t)stream, a, SpecArg<false>{});
+  return (int)hipGetLastError();
+}
+
+namespace {
+
+// the spec must describe exactly the base shape
+inline bool spec_ok(const void* spec, int B, int S, int H, int dh) {
+  if (!spec) return false;
+  const SpliceSpec* sp = (const SpliceSpec*)spec;
+  if (sp->shape[0] != B || sp->shape[1] != S || sp->shape[2] != H || sp->shape[3] != dh) return false;
+  for (int d = 0; d < 4; ++d)
+    if (sp->nr[d] < 0 || sp->nr[d] > 8) return false;
+  return true;
+}
+
+}  // namespace
+
+// iit_attn_f32_fwd over B2 = 2B batches, rows [0, B) base and [B, 2B) source, with an interchange splice of z in
+// the store: ``spec`` (host pointer to one SpliceSpec over the base shape [B][S][H][dh], copied into the kernel
+// arguments; ``sstride`` is not read) selects the elements of a base row that take the source row's value.  Every
+// wave computes and writes its lse as the plain kernel does.  strides: as iit_attn_f32_fwd.
+IIT_EXPORT int iit_attn_f32_fwd_pair(const void* q, const void* k, const void* v, void* z, void* lse,
+                                     const long* strides, int B2, int S, int H, int dh, float scale, int causal,
+                                     const void* spec, void* stream) {
+  if (!strides || !aligned4(lse) || !iit_attn_f32_ok(q, k, v, z, B2, S, H, dh) || (B2 & 1) ||
+      !spec_ok(spec, B2 / 2, S, H, dh))
+    return (int)hipErrorInvalidValue;
+  AttnF32Args a = {};
+  a.q = (const float*)q; a.k = (const float*)k; a.v = (const float*)v;
+  a.z = (float*)z; a.lse = (float*)lse;
+  const Str3* s = (const Str3*)strides;
+  a.sq = s[0]; a.sk = s[1]; a.sv = s[2]; a.sz = s[3];
+  a.B = B2; a.S = S; a.H = H; a.dh = dh;
+  a.scale = scale; a.causal = causal;
+  a.waves = waves_for(S, dh, false);
+  const size_t lds = a.waves * wave_floats(S, dh, false) * sizeof(float);
+  const SpecArg<true> sp = {*(const SpliceSpec*)spec};
+  hipLaunchKernelGGL(attn_f32_fwd_kernel<true>, dim3(cdiv((long)B2 * H, a.waves)), dim3(64 * a.waves), lds,
+                     (hipStream_t)stream, a, sp);
+  return (int)hipGetLastError();
+}
+
+// iit_attn_f32_bwd with the spec-selected elements of dO ([B][S][H][dh]) taken as +0: the backward of the base rows
+// of iit_attn_f32_fwd_pair.  strides: as iit_attn_f32_bwd.
+IIT_EXPORT int iit_attn_f32_bwd_masked(const void* q, const void* k, const void* v, const void* dout,
+                                       const void* lse, void* dq, void* dk, void* dv, const long* strides, int B,
+                                       int S, int H, int dh, float scale, int causal, const void* spec,
+                                       void* stream) {
+  if (!strides || !aligned4(lse) || !aligned4(dq) || !aligned4(dk) || !aligned4(dv) ||
+      !iit_attn_f32_ok(q, k, v, dout, B, S, H, dh) || !spec_ok(spec, B, S, H, dh))
+    return (int)hipErrorInvalidValue;
+  AttnF32Args a = {};
+  a.q = (const float*)q; a.k = (const float*)k; a.v = (const float*)v;
+  a.dout = (const float*)dout; a.lse_in = (const float*)lse;
+  a.dq = (float*)dq; a.dk = (float*)dk; a.dv = (float*)dv;
+  const Str3* s = (const Str3*)strides;
+  a.sq = s[0]; a.sk = s[1]; a.sv = s[2]; a.sdo = s[3]; a.sdq = s[4]; a.sdk = s[5]; a.sdv = s[6];
+  a.B = B; a.S = S; a.H = H; a.dh = dh;
+  a.scale = scale; a.causal = causal;
+  a.waves = waves_for(S, dh, true);
+  const size_t lds = a.waves * wave_floats(S, dh, true) * sizeof(float);
+  const SpecArg<true> sp = {*(const SpliceSpec*)spec};
+  hipLaunchKernelGGL(attn_f32_bwd_kernel<true>, dim3(cdiv((long)B * H, a.waves)), dim3(64 * a.waves), lds,
+                     (hipStream_t)stream, a, sp);
   return (int)hipGetLastError();
 }

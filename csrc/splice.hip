@@ -121,8 +121,8 @@ __device__ __forceinline__ int range_coord(const SpliceSpec& sp, int d, int k) {
   return sp.lo[d][0];
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void sparse_pair_kernel(__bf16* __restrict__ act, long T, long ld, SpliceSpec sp,
+template <typename E, int MODE>
+__global__ __launch_bounds__(256) void sparse_pair_kernel(E* __restrict__ act, long T, long ld, SpliceSpec sp,
                                                           long total, int n1, int n2, int n3) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -135,10 +135,11 @@ __global__ __launch_bounds__(256) void sparse_pair_kernel(__bf16* __restrict__ a
   const int c3 = range_coord(sp, 3, k3);
   const long row = ((long)c0 * sp.shape[1] + c1) * sp.shape[2] + c2;
   if (MODE == 0) act[row * ld + c3] = act[(row + T) * ld + c3];
-  else act[row * ld + c3] = f2bf(0.f);
+  else act[row * ld + c3] = st_f<E>(0.f);
 }
 
-IIT_EXPORT int iit_sparse_pair(void* act, long T, long ld, const void* spec, int mode, void* stream) {
+template <typename E>
+static int sparse_pair_launch(void* act, long T, long ld, const void* spec, int mode, void* stream) {
   const SpliceSpec sp = *(const SpliceSpec*)spec;
   long cnt[4];
   long total = 1;
@@ -152,10 +153,30 @@ IIT_EXPORT int iit_sparse_pair(void* act, long T, long ld, const void* spec, int
   const dim3 grid((unsigned)((total + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
   if (mode == 0)
-    hipLaunchKernelGGL(sparse_pair_kernel<0>, grid, dim3(256), 0, s, (__bf16*)act, T, ld, sp, total, (int)cnt[1],
+    hipLaunchKernelGGL((sparse_pair_kernel<E, 0>), grid, dim3(256), 0, s, (E*)act, T, ld, sp, total, (int)cnt[1],
                        (int)cnt[2], (int)cnt[3]);
   else
-    hipLaunchKernelGGL(sparse_pair_kernel<1>, grid, dim3(256), 0, s, (__bf16*)act, T, ld, sp, total, (int)cnt[1],
+    hipLaunchKernelGGL((sparse_pair_kernel<E, 1>), grid, dim3(256), 0, s, (E*)act, T, ld, sp, total, (int)cnt[1],
                        (int)cnt[2], (int)cnt[3]);
   return hipGetLastError();
+}
+
+IIT_EXPORT int iit_sparse_pair(void* act, long T, long ld, const void* spec, int mode, void* stream) {
+  return sparse_pair_launch<__bf16>(act, T, ld, spec, mode, stream);
+}
+
+// The fp32 twin (the paired forward of the fp32 op backend, iit_amd/ops/hip32_ops.py MlpInF32PairFn): act is fp32
+// [2T][ld] (mode 0) or [T][ld] (mode 1).  Refuses a null operand, a spec whose leading three dimensions do not give
+// T rows, and a last dimension wider than ld.
+IIT_EXPORT int iit_sparse_pair_f32(void* act, long T, long ld, const void* spec, int mode, void* stream) {
+  if (!act || !spec || ((uintptr_t)act & 3) || T < 1 || (mode != 0 && mode != 1)) return (int)hipErrorInvalidValue;
+  const SpliceSpec* sp = (const SpliceSpec*)spec;
+  if (sp->shape[3] > ld) return (int)hipErrorInvalidValue;
+  for (int d = 0; d < 4; ++d) {
+    if (sp->nr[d] < 0 || sp->nr[d] > 8) return (int)hipErrorInvalidValue;
+    for (int r = 0; r < sp->nr[d]; ++r)
+      if (sp->lo[d][r] < 0 || sp->hi[d][r] > sp->shape[d] || sp->lo[d][r] > sp->hi[d][r])
+        return (int)hipErrorInvalidValue;
+  }
+  return sparse_pair_launch<float>(act, T, ld, spec, mode, stream);
 }

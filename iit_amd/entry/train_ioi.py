@@ -41,11 +41,12 @@ def parse(argv=None):
     ap.add_argument("--dtype", default=None, choices=["fp32", "bf16"],
                     help="compute dtype (default: bf16 on GPU for gpt2-small, fp32 otherwise)")
     ap.add_argument("--engine", default="native", choices=["native", "reference"])
-    ap.add_argument("--fp32-backend", default="torch", choices=["torch", "hip32", "hip32x", "hip32n"],
+    ap.add_argument("--fp32-backend", default="torch", choices=["torch", "hip32", "hip32x", "hip32n", "hip32p"],
                     help="op backend of an fp32 run with the native engine: library GEMMs (torch), the exact-fp32 "
                          "MFMA GEMM of csrc/gemm_f32.hip (hip32), that plus the fp32 attention kernel of "
                          "csrc/attn_fp32.hip (hip32x), or that plus LayerNorm, the GELU epilogues and the residual "
-                         "epilogues of csrc/block_f32.hip and csrc/gemm_f32.hip (hip32n)")
+                         "epilogues of csrc/block_f32.hip and csrc/gemm_f32.hip (hip32n), or that plus the paired "
+                         "source + base forward of an interchange intervention (hip32p)")
     ap.add_argument("--wandb", action="store_true")
     ap.add_argument("--save-root", default="models/ioi")
     ap.add_argument("--checkpoint-dir", default=None)
@@ -79,7 +80,7 @@ def main(argv=None):
     dtype = args.dtype or ("bf16" if (dev.type == "cuda" and args.model == "gpt2-small") else "fp32")
     ll_cfg.update(init_weights=True, device=str(dev), dtype=torch.bfloat16 if dtype == "bf16" else torch.float32)
     ll_model = HookedTransformer(ll_cfg)
-    if dtype == "fp32" and args.engine == "native" and args.fp32_backend in ("hip32", "hip32x", "hip32n"):
+    if dtype == "fp32" and args.engine == "native" and args.fp32_backend in ("hip32", "hip32x", "hip32n", "hip32p"):
         # opt-in: the projections (hip32x: attention too; hip32n: the whole block) on the exact-fp32 kernels (needs a GPU)
         ll_model.set_op_backend(args.fp32_backend)
     elif dtype == "fp32" or args.engine == "reference":

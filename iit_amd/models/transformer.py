@@ -879,6 +879,9 @@ class HookedTransformer(HookedRootModule):
             return None
         if any(hp.is_live for hp in self.hook_dict.values()):
             return None
+        model_ok = getattr(ops, "pair_model_ok", None)  # a backend's own conditions on the model (hip32p)
+        if model_ok is not None and not model_ok(self, tokens):
+            return None
         B, S = tokens.shape
         order = []
         for name, idxs in sites.items():

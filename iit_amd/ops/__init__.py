@@ -13,6 +13,11 @@
   block on the repo's kernels when no hook inside the op is live: LayerNorm (``csrc/block_f32.hip``),
   ``gelu_new`` and its derivative in ``gemm_f32`` epilogues, both residual adds in the projections'
   epilogues.  Opt-in under ``hip32``'s rules.
+* ``hip32p`` – :class:`iit_amd.ops.hip32_ops.HipF32POps`, ``hip32n`` with the paired forward: an interchange
+  intervention is one forward of 2B rows up to its deepest site (``HookedTransformer.run_paired``), the ``hook_z``
+  splice and its gradient mask inside the fp32 attention kernels, an ``mlp.hook_post`` splice as a sparse copy.
+  Models it does not cover (QKV outside an arena, S or d_head above 64, ``d_mlp % 4 != 0``) run the two forwards.
+  Opt-in under ``hip32``'s rules.
 
 ``select_ops(model, backend)`` picks per call: ``backend=None`` means "hip when
 the model lives on a GPU and computes in bf16, else torch".  Asking for ``hip``
@@ -60,11 +65,12 @@ def select_ops(model, backend: Optional[str] = None):
             raise RuntimeError("hip op backend requires the model on a GPU")
         from .hip_ops import get_hip_ops
         return get_hip_ops(model)
-    if backend in ("hip32", "hip32x", "hip32n"):  # opt-in only: ``backend=None`` never selects them
+    if backend in ("hip32", "hip32x", "hip32n", "hip32p"):  # opt-in only: ``backend=None`` never selects them
         if not on_gpu:
             raise RuntimeError(f"{backend} op backend requires the model on a GPU")
-        from .hip32_ops import get_hip32_ops, get_hip32n_ops, get_hip32x_ops
-        return {"hip32": get_hip32_ops, "hip32x": get_hip32x_ops, "hip32n": get_hip32n_ops}[backend](model)
+        from .hip32_ops import get_hip32_ops, get_hip32n_ops, get_hip32p_ops, get_hip32x_ops
+        return {"hip32": get_hip32_ops, "hip32x": get_hip32x_ops, "hip32n": get_hip32n_ops,
+                "hip32p": get_hip32p_ops}[backend](model)
     raise ValueError(f"unknown op backend {backend}")
 
 

@@ -14,12 +14,19 @@ stay where the fp32 torch path has them.  Gradients are returned to autograd exa
 ``csrc/block_f32.hip`` (:class:`LayerNormF32Fn`), ``gelu_new`` in the W_in GEMM's epilogue (:class:`MlpInF32Fn`),
 its derivative in the ``dY W_out^T`` GEMM's epilogue (:class:`MlpGeluResidualF32Fn`) and both residual adds in the
 projections' epilogues (``LinearF32Fn``'s ``resid``).  Opt-in in the same way.
+
+``hip32p`` (:class:`HipF32POps`) is ``hip32n`` plus the paired forward: an interchange intervention runs as one
+forward of 2B rows up to its deepest site (``HookedTransformer.run_paired``), with the ``hook_z`` splice in the store of
+``csrc/attn_fp32.hip``'s paired forward, its gradient mask in the staging of the masked backward, and an
+``mlp.hook_post`` splice as a sparse copy (``iit_sparse_pair_f32``).  Opt-in in the same way.
 """
 from __future__ import annotations
 
 import torch
 
 from . import hip_kernels as K
+from .hip_ops import Paired, PairSpliceFn, _one, pair_specs
+from .splice import PatchSpec, patch_spec
 from .torch_ops import TorchOps, act_fn
 
 
@@ -514,6 +521,319 @@ class HipF32NOps(HipF32XOps):
         return self.mlp_out_residual(post, W_out, b_out, resid)
 
 
+# ------------------------------------------------------------------------------ hip32p: paired source + base rows
+# Each paired Function derives from the unpaired one: the forward runs the same kernel once over the 2B / 2T rows
+# (rows [0, B) base, [B, 2B) source), returns the base rows, puts the full result in ``box`` and saves base-row slices
+# only, so the backward is the unpaired backward on the tensors the unpaired forward would have saved.
+
+
+def _base_rows(x: torch.Tensor) -> int:
+    return x.numel() // x.shape[-1]
+
+
+class LayerNormF32PairFn(LayerNormF32Fn):
+    @staticmethod
+    def forward(ctx, x, w, b, eps, x_full, box):
+        d = x.shape[-1]
+        x2 = _rows(x_full.detach(), d)
+        T2, T = x2.shape[0], _base_rows(x)
+        y = torch.empty(T2, d, dtype=torch.float32, device=x.device)
+        mean = torch.empty(T2, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(T2, dtype=torch.float32, device=x.device)
+        wd = None if w is None else w.detach()
+        K.ln_f32_fwd(x2, wd, None if b is None else b.detach(), y, mean, rstd, eps)
+        ctx.save_for_backward(x2[:T], mean[:T], rstd[:T], wd)
+        ctx.shape = x.shape
+        yf = y.view(x_full.shape)
+        box.append(yf)
+        return yf[:x.shape[0]]
+
+    @staticmethod
+    def backward(ctx, dy):
+        return LayerNormF32Fn.backward(ctx, dy) + (None, None)
+
+
+class QKVF32PairFn(QKVF32Fn):
+    @staticmethod
+    def forward(ctx, x, W_Q, W_K, W_V, b_Q, b_K, b_V, x_full, box):
+        H, d, dh = W_Q.shape
+        Hkv = W_K.shape[0]
+        N = (H + 2 * Hkv) * dh
+        Wp = W_Q.detach().as_strided((d, N), (N, 1))
+        bp = b_Q.detach().as_strided((N,), (1,))
+        x2 = _operand(x_full.detach().reshape(-1, d))
+        ctx.save_for_backward(x2[:_base_rows(x)], Wp)
+        ctx.lead, ctx.dims = x.shape[:-1], (H, Hkv, dh)
+        lead = x_full.shape[:-1]
+        yf = _forward(x2, Wp, bp).view(*lead, N)
+        box.append((yf[..., :H * dh].view(*lead, H, dh), yf[..., H * dh:(H + Hkv) * dh].view(*lead, Hkv, dh),
+                    yf[..., (H + Hkv) * dh:].view(*lead, Hkv, dh)))
+        return tuple(t[:x.shape[0]] for t in box[0])
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        return QKVF32Fn.backward(ctx, dq, dk, dv) + (None, None)
+
+
+class AttentionF32PairFn(AttentionF32Fn):
+    """Attention over the 2B rows.  ``spec`` (a ``PatchSpec`` over the base ``[B][S][H][dh]``, or None): the
+    interchange splice of ``hook_z`` in the kernel's store (``attn_f32_fwd_pair``), and its gradient mask in the
+    staging of dO (``attn_f32_bwd_masked``).  Without one: the plain forward and the plain backward."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, causal, scale, spec, q_full, k_full, v_full, box):
+        qf, kf, vf = (_unit_last(t.detach()) for t in (q_full, k_full, v_full))
+        B2, S, H, dh = qf.shape
+        B = q.shape[0]
+        z = torch.empty(B2, S, H, dh, dtype=torch.float32, device=q.device)
+        lse = torch.empty(B2, H, S, dtype=torch.float32, device=q.device)
+        if spec is None:
+            K.attn_f32_fwd(qf, kf, vf, z, lse, scale, causal)
+        else:
+            K.attn_f32_fwd_pair(qf, kf, vf, z, lse, scale, causal, spec)
+        ctx.save_for_backward(qf[:B], kf[:B], vf[:B], lse[:B])
+        ctx.causal, ctx.scale, ctx.spec = bool(causal), float(scale), spec
+        box.append(z)
+        return z[:B]
+
+    @staticmethod
+    def backward(ctx, dz):
+        if ctx.spec is None:
+            return AttentionF32Fn.backward(ctx, dz) + (None,) * 5
+        q, k, v, lse = ctx.saved_tensors
+        dq, dk, dv = (torch.empty(q.shape, dtype=torch.float32, device=q.device) for _ in range(3))
+        K.attn_f32_bwd_masked(q, k, v, _unit_last(dz), lse, dq, dk, dv, ctx.scale, ctx.causal, ctx.spec)
+        need = ctx.needs_input_grad
+        return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None) + (None,) * 7
+
+
+class LinearF32PairFn(LinearF32Fn):
+    @staticmethod
+    def forward(ctx, x, W2, b, resid, x_full, resid_full, box):
+        Kd, N = W2.shape
+        x2 = _operand(x_full.detach().reshape(-1, Kd))
+        r2 = None if resid_full is None else _operand(resid_full.detach().reshape(-1, N))
+        ctx.save_for_backward(x2[:_base_rows(x)], W2)
+        ctx.lead, ctx.has_b, ctx.has_r = x.shape[:-1], b is not None, resid is not None
+        yf = _forward(x2, W2, b, r2).view(*x_full.shape[:-1], N)
+        box.append(yf)
+        return yf[:x.shape[0]]
+
+    @staticmethod
+    def backward(ctx, dy):
+        return LinearF32Fn.backward(ctx, dy) + (None, None, None)
+
+
+class MlpInF32PairFn(MlpInF32Fn):
+    """``spec`` (a ``PatchSpec`` over the base ``[B][S][d_mlp]``, or None): the interchange splice of
+    ``mlp.hook_post`` inside the op -- ``sparse_pair_f32`` copies the selected elements of the source half into the
+    base half right after the GEMM, and zeroes them in ``dpost`` before the dgelu."""
+
+    @staticmethod
+    def forward(ctx, x, W_in, b_in, x_full, spec, box):
+        Kd, N = W_in.shape
+        x2 = _operand(x_full.detach().reshape(-1, Kd))
+        T = _base_rows(x)
+        pre, post = _mlp_in_forward(x2, W_in.detach(), None if b_in is None else b_in.detach())
+        if spec is not None:
+            K.sparse_pair_f32(post, T, N, spec, 0)
+        ctx.save_for_backward(x2[:T], W_in.detach(), pre[:T])
+        ctx.lead, ctx.has_b, ctx.spec = x.shape[:-1], b_in is not None, spec
+        pf = post.view(*x_full.shape[:-1], N)
+        box.append(pf)
+        return pf[:x.shape[0]]
+
+    @staticmethod
+    def backward(ctx, dpost):
+        if ctx.spec is not None:
+            N = dpost.shape[-1]
+            dpost = dpost.reshape(-1, N).clone(memory_format=torch.contiguous_format)
+            K.sparse_pair_f32(dpost, dpost.shape[0], N, ctx.spec, 1)
+        return MlpInF32Fn.backward(ctx, dpost) + (None, None, None)
+
+
+class MlpGeluResidualF32PairFn(MlpGeluResidualF32Fn):
+    @staticmethod
+    def forward(ctx, x, W_in, b_in, W_out, b_out, resid, x_full, resid_full, box):
+        d, dm = W_in.shape
+        n_out = W_out.shape[1]
+        x2 = _operand(x_full.detach().reshape(-1, d))
+        r2 = _operand(resid_full.detach().reshape(-1, n_out))
+        W_in, W_out = W_in.detach(), W_out.detach()
+        T = _base_rows(x)
+        pre, post = _mlp_in_forward(x2, W_in, None if b_in is None else b_in.detach())
+        y = _forward(post, W_out, None if b_out is None else b_out.detach(), r2)
+        ctx.save_for_backward(x2[:T], W_in, W_out, pre[:T], post[:T])
+        ctx.lead, ctx.has_b = x.shape[:-1], (b_in is not None, b_out is not None)
+        yf = y.view(*resid_full.shape[:-1], n_out)
+        box.append(yf)
+        return yf[:resid.shape[0]]
+
+    @staticmethod
+    def backward(ctx, dy):
+        return MlpGeluResidualF32Fn.backward(ctx, dy) + (None, None, None)
+
+
+def _heads_spec(heads, shape):
+    """The ``PatchSpec`` over ``shape = (B, S, H, dh)`` that selects whole heads (none for an empty list)."""
+    runs = []
+    for h in sorted(set(int(h) for h in heads)):
+        if runs and runs[-1][1] == h:
+            runs[-1] = (runs[-1][0], h + 1)
+        else:
+            runs.append((h, h + 1))
+    if len(runs) > 8:
+        return None
+    return PatchSpec([(n, runs if i == 2 else [(0, n)], 0) for i, n in enumerate(shape)])
+
+
+class HipF32POps(HipF32NOps):
+    """:class:`HipF32NOps` with the paired forward: an interchange intervention as one forward of 2B rows up to the
+    deepest site (``HookedTransformer.run_paired`` / ``TransformerBlock.forward_paired``, the protocol of
+    ``HipOps``), on the fp32 kernels.  The ``hook_z`` splice and its gradient mask run inside the attention kernels
+    (``csrc/attn_fp32.hip`` ``iit_attn_f32_fwd_pair`` / ``iit_attn_f32_bwd_masked``), an ``mlp.hook_post`` splice as
+    one thread per selected element (``iit_sparse_pair_f32``).  Everything else is ``hip32n``.  ``calls`` (its own
+    dictionary) also counts the paired ops (``"pair_embed"``, ``"pair_layer_norm"``, ``"pair_qkv"``,
+    ``"pair_attention"``, ``"pair_o_proj"``, ``"pair_mlp_in"``, ``"pair_mlp_fused"``, ``"pair_mlp_out"``,
+    ``"pair_splice"``) and ``"paired_fallback"``: a ``run_paired`` that ``pair_model_ok`` sent back to the two
+    forwards before any paired op ran."""
+    name = "hip32p"
+    fused = False
+    supports_pairs = True
+    calls: dict = {}
+
+    # -- the parts of the protocol that only the bf16 backend needs
+    def begin_forward(self):
+        pass
+
+    def fwd_prefetch(self, *Ws):
+        return None
+
+    def layer_norm(self, x, w, b, eps, prefetch=None, **kw):
+        return super().layer_norm(x, w, b, eps, **kw)
+
+    def qkv(self, x, W_Q, W_K, W_V, b_Q, b_K, b_V):
+        q, k, v = super().qkv(x, W_Q, W_K, W_V, b_Q, b_K, b_V)
+        q._iit_kv = (k, v)  # for attention_dual, which is handed q alone
+        return q, k, v
+
+    def pair_heads_ok(self, S: int, dh: int) -> bool:
+        return 1 <= S <= K.ATTN_F32_MAX_S and 1 <= dh <= K.ATTN_F32_MAX_DH
+
+    def pair_model_ok(self, model, tokens) -> bool:
+        """Whether ``model`` can run paired on this backend: fp32 on the GPU, S <= 64, d_head <= 64,
+        ``d_mlp % 4 == 0``, QKV packed in an arena, the ``-inf`` masked fill.  Counts a refusal as
+        ``"paired_fallback"``."""
+        cfg = model.cfg
+        ok = (cfg.dtype == torch.float32 and model.embed.W_E.is_cuda and model.embed.W_E.dtype == torch.float32
+              and tokens.dim() == 2 and self.pair_heads_ok(tokens.shape[1], cfg.d_head)
+              and (cfg.attn_only or cfg.d_mlp % 4 == 0) and cfg.d_model % 4 == 0)
+        for blk in model.blocks if ok else ():
+            a = blk.attn
+            ps = (a.W_Q, a.W_K, a.W_V, a.b_Q, a.b_K, a.b_V)
+            lns = [ln for ln in (blk.ln1, None if cfg.attn_only else blk.ln2) if ln is not None and ln.w is not None]
+            if not (all(p is not None and p.is_cuda and p.dtype == torch.float32 and self.w(p) is p for p in ps)
+                    and packed_qkv(*ps) and a.ignore_value() == float("-inf") and a.W_O.is_contiguous()
+                    and all(ln.b is not None and self._param(ln.w) and self._param(ln.b) for ln in lns)):
+                ok = False
+                break
+        if not ok:
+            self._count("paired_fallback")
+        return ok
+
+    # -- paired ops
+    def pair_embed_pos(self, tokens, src_tokens, W_E, W_pos):
+        B, S = tokens.shape
+        self._count("pair_embed")
+        base = self.residual(self.embed(tokens, W_E), self.pos_embed(B, S, W_pos))
+        with torch.no_grad():
+            src = self.residual(self.embed(src_tokens, W_E), self.pos_embed(B, S, W_pos))
+            full = torch.cat([base.detach(), src])
+        return Paired(base, full)
+
+    def pair_layer_norm_fork(self, p, w, b, eps, prefetch=None):
+        self._count("pair_layer_norm")
+        y, yf = _one(LayerNormF32PairFn, p.base, w, b, eps, p.full)
+        return Paired(y, yf), p
+
+    def pair_qkv(self, p, W_Q, W_K, W_V, b_Q, b_K, b_V):
+        self._count("pair_qkv")
+        base, full = _one(QKVF32PairFn, p.base, W_Q, W_K, W_V, b_Q, b_K, b_V, p.full)
+        return tuple(Paired(b_, f) for b_, f in zip(base, full))
+
+    def _pair_attention(self, qkv, causal, attn_scale, spec):
+        q, k, v = qkv
+        self._count("pair_attention")
+        z, zf = _one(AttentionF32PairFn, q.base, k.base, v.base, causal, 1.0 / attn_scale, spec, q.full, k.full,
+                     v.full)
+        return Paired(z, zf)
+
+    def pair_attention(self, qkv, causal: bool, attn_scale: float, heads=None):
+        """Attention over paired rows; ``heads``: the base rows of these heads take the source rows' z."""
+        spec = None
+        if heads:
+            B2, S, H, dh = qkv[0].full.shape
+            spec = _heads_spec(heads, (B2 // 2, S, H, dh))
+            if spec is None:
+                raise RuntimeError(f"hip32p: the head list {list(heads)} needs more than 8 ranges")
+        return self._pair_attention(qkv, causal, attn_scale, spec)
+
+    def pair_attention_spliced(self, qkv, causal: bool, attn_scale: float, index):
+        """Attention over paired rows with ``hook_z[index]`` of the base rows taken from the source rows in the
+        kernel's store; None when the range table cannot express ``index`` (the caller splices in a pass)."""
+        B2, S, H, dh = qkv[0].full.shape
+        spec = patch_spec(index, (B2 // 2, S, H, dh))
+        if spec is None or [d[0] for d in spec.dims] != [B2 // 2, S, H, dh]:
+            return None
+        return self._pair_attention(qkv, causal, attn_scale, spec)
+
+    def attention_dual(self, q, causal: bool, attn_scale: float) -> torch.Tensor:
+        """No-grad attention of the source rows behind ``q`` (``qkv``'s output), copied into both halves of a
+        ``[2B][S][H][dh]`` tensor: the z of a whole-layer ``hook_z`` splice."""
+        k, v = q._iit_kv
+        z = self.attention(q, k, v, causal, attn_scale)
+        return torch.cat([z, z])
+
+    def pair_splice(self, p, index):
+        if not p.full.is_contiguous():
+            return None
+        specs = pair_specs(index, tuple(p.base.shape))
+        if specs is None:
+            return None
+        self._count("pair_splice")
+        out, full = _one(PairSpliceFn, p.base, p.full, specs[0], specs[1])
+        return Paired(out, full)
+
+    def pair_o_proj_residual(self, z, W_O, b_O, resid):
+        H, dh, d = W_O.shape
+        self._count("pair_o_proj")
+        out, full = _one(LinearF32PairFn, z.base.reshape(*z.base.shape[:-2], H * dh), W_O.view(H * dh, d), b_O,
+                         resid.base, z.full.reshape(*z.full.shape[:-2], H * dh), resid.full)
+        return Paired(out, full)
+
+    def pair_mlp_in(self, x, W_in, b_in, erf: bool = False, index=None):
+        """Paired W_in + gelu_new.  ``index`` (optional): an ``mlp.hook_post`` splice applied inside the op; None
+        when the range table cannot express it (the caller then splices in a pass)."""
+        spec = None
+        if index is not None:
+            spec = patch_spec(index, tuple(x.base.shape[:-1]) + (W_in.shape[1],))
+            if spec is None:
+                return None
+        self._count("pair_mlp_in")
+        post, pf = _one(MlpInF32PairFn, x.base, W_in, b_in, x.full, spec)
+        return None, Paired(post, pf)
+
+    def pair_mlp_out_residual(self, post, W_out, b_out, resid):
+        self._count("pair_mlp_out")
+        out, full = _one(LinearF32PairFn, post.base, W_out, b_out, resid.base, post.full, resid.full)
+        return Paired(out, full)
+
+    def pair_mlp_gelu_residual(self, x, W_in, b_in, W_out, b_out, resid, erf: bool = False):
+        self._count("pair_mlp_fused")
+        out, full = _one(MlpGeluResidualF32PairFn, x.base, W_in, b_in, W_out, b_out, resid.base, x.full, resid.full)
+        return Paired(out, full)
+
+
 _OPS = {}
 
 
@@ -539,3 +859,8 @@ def get_hip32x_ops(model) -> HipF32XOps:
 def get_hip32n_ops(model) -> HipF32NOps:
     """``hip32n`` under the same rules as :func:`get_hip32_ops`."""
     return _get(HipF32NOps, model)
+
+
+def get_hip32p_ops(model) -> HipF32POps:
+    """``hip32p`` under the same rules as :func:`get_hip32_ops`."""
+    return _get(HipF32POps, model)

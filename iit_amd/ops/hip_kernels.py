@@ -48,6 +48,9 @@ _SIGS = {
     "iit_attn_f32_ok": [c_void_p] * 4 + [c_int] * 4,
     "iit_attn_f32_fwd": [c_void_p] * 6 + [c_int] * 4 + [c_float, c_int, c_void_p],
     "iit_attn_f32_bwd": [c_void_p] * 9 + [c_int] * 4 + [c_float, c_int, c_void_p],
+    "iit_attn_f32_fwd_pair": [c_void_p] * 6 + [c_int] * 4 + [c_float, c_int, c_void_p, c_void_p],
+    "iit_attn_f32_bwd_masked": [c_void_p] * 9 + [c_int] * 4 + [c_float, c_int, c_void_p, c_void_p],
+    "iit_sparse_pair_f32": [c_void_p, c_long, c_long, c_void_p, c_int, c_void_p],
     "iit_gemm_glds_ok": [c_void_p] * 5 + [c_long] * 5 + [c_int] * 9,
     "iit_gemm_glds_sm": [c_void_p] * 8 + [c_long] * 5 + [c_int] * 8 + [c_void_p] * 3 + [c_int] + [c_void_p] * 3,
     "iit_embed_pos_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
@@ -639,6 +642,80 @@ def attn_f32_bwd(q, k, v, do, lse, dq, dk, dv, scale: float, causal: bool):
     _check(lib().iit_attn_f32_bwd(_p(q), _p(k), _p(v), _p(do), _p(lse), _p(dq), _p(dk), _p(dv),
                                   _strides3(q, k, v, do, dq, dk, dv), B, S, H, dh, scale, int(causal), _stream()),
            "iit_attn_f32_bwd")
+
+
+def _attn_f32_spec_why(spec, shape) -> Optional[str]:
+    """Why ``spec`` (a :class:`iit_amd.ops.splice.PatchSpec`) is not a range table over exactly ``shape``."""
+    if spec is None or not getattr(spec, "ptr", 0):
+        return "spec must be a PatchSpec, got None"
+    got = tuple(int(d[0]) for d in spec.dims)
+    if got != tuple(shape):
+        return f"spec is over shape {got}, expected the base shape {tuple(shape)}"
+    return None
+
+
+def _attn_f32_bounds(what: str, ts: dict, lse):
+    if CHECK_BOUNDS:
+        for name, t in ts.items():
+            B, S, H, dh = t.shape
+            need = (B - 1) * t.stride(0) + (S - 1) * t.stride(1) + (H - 1) * t.stride(2) + dh
+            if min(t.stride()[:3]) < 0 or need > _avail(t):
+                raise RuntimeError(f"{what}: operand {name} needs {need} elements, storage holds {_avail(t)} "
+                                   f"(shape {tuple(t.shape)}, stride {t.stride()})")
+        _bounds(what, ("lse", lse, 1, lse.numel(), lse.numel()))
+
+
+def _attn_f32_fwd_pair_why(ts: dict, lse, spec) -> Optional[str]:
+    why = _attn_f32_why(ts)
+    if why is not None:
+        return why
+    B2, S, H, dh = ts["q"].shape
+    if B2 % 2:
+        return f"the batch of a paired forward holds base rows then source rows: {B2} is odd"
+    if not (lse.is_cuda and lse.dtype == torch.float32 and tuple(lse.shape) == (B2, H, S) and lse.is_contiguous()):
+        return f"lse must be contiguous fp32 [B2][H][S] on the GPU, got {lse.dtype} {tuple(lse.shape)}"
+    return _attn_f32_spec_why(spec, (B2 // 2, S, H, dh))
+
+
+def attn_f32_fwd_pair(q, k, v, z, lse, scale: float, causal: bool, spec):
+    """:func:`attn_f32_fwd` over ``[2B][S][H][dh]`` operands, rows ``[0, B)`` base and ``[B, 2B)`` source, with the
+    interchange splice of z in the kernel's store: the elements of ``z[:B]`` that ``spec`` (a ``PatchSpec`` over
+    ``(B, S, H, dh)``) selects are the source rows' values.  ``z[B:]`` and all of ``lse`` are the plain forward's.
+    Raises ``ValueError``, without launching, for an odd batch, a missing spec, a spec over another shape and
+    everything :func:`attn_f32_fwd` refuses."""
+    ts = {"q": q, "k": k, "v": v, "z": z}
+    why = _attn_f32_fwd_pair_why(ts, lse, spec)
+    if why is not None:
+        raise ValueError(f"attn_f32_fwd_pair: {why}")
+    _attn_f32_bounds("attn_f32_fwd_pair", ts, lse)
+    B2, S, H, dh = q.shape
+    _check(lib().iit_attn_f32_fwd_pair(_p(q), _p(k), _p(v), _p(z), _p(lse), _strides3(q, k, v, z), B2, S, H, dh,
+                                       scale, int(causal), spec.ptr, _stream()), "iit_attn_f32_fwd_pair")
+
+
+def _attn_f32_bwd_masked_why(ts: dict, lse, spec) -> Optional[str]:
+    why = _attn_f32_why(ts)
+    if why is not None:
+        return why
+    B, S, H, dh = ts["q"].shape
+    if not (lse.is_cuda and lse.dtype == torch.float32 and tuple(lse.shape) == (B, H, S) and lse.is_contiguous()):
+        return f"lse must be contiguous fp32 [B][H][S] on the GPU, got {lse.dtype} {tuple(lse.shape)}"
+    return _attn_f32_spec_why(spec, (B, S, H, dh))
+
+
+def attn_f32_bwd_masked(q, k, v, do, lse, dq, dk, dv, scale: float, causal: bool, spec):
+    """:func:`attn_f32_bwd` with the elements of ``do`` that ``spec`` (a ``PatchSpec`` over ``(B, S, H, dh)``)
+    selects taken as +0 whatever they hold: the backward of the base rows of :func:`attn_f32_fwd_pair`.  Same
+    refusals as :func:`attn_f32_bwd`, and a missing spec or one over another shape."""
+    ts = {"q": q, "k": k, "v": v, "do": do, "dq": dq, "dk": dk, "dv": dv}
+    why = _attn_f32_bwd_masked_why(ts, lse, spec)
+    if why is not None:
+        raise ValueError(f"attn_f32_bwd_masked: {why}")
+    _attn_f32_bounds("attn_f32_bwd_masked", ts, lse)
+    B, S, H, dh = q.shape
+    _check(lib().iit_attn_f32_bwd_masked(_p(q), _p(k), _p(v), _p(do), _p(lse), _p(dq), _p(dk), _p(dv),
+                                         _strides3(q, k, v, do, dq, dk, dv), B, S, H, dh, scale, int(causal),
+                                         spec.ptr, _stream()), "iit_attn_f32_bwd_masked")
 
 
 # ------------------------------------------------------------------------------ dual GEMM (csrc/gemm_dual.hip)
@@ -1254,6 +1331,41 @@ def sparse_pair(act, T: int, ld: int, spec_ptr, mode: int) -> None:
     if CHECK_BOUNDS:
         _bounds("sparse_pair", ("act", act, 2 * T if mode == 0 else T, ld, ld))
     _check(lib().iit_sparse_pair(_p(act), T, ld, spec_ptr, int(mode), _stream()), "sparse_pair")
+
+
+def _sparse_pair_f32_why(act, T: int, ld: int, spec, mode: int) -> Optional[str]:
+    """Why ``iit_sparse_pair_f32`` does not take the operands (None when it does)."""
+    if mode not in (0, 1):
+        return f"mode must be 0 (copy) or 1 (zero), got {mode}"
+    if not isinstance(act, torch.Tensor) or not act.is_cuda or act.dtype != torch.float32:
+        return "act must be an fp32 tensor on the GPU"
+    if spec is None or not getattr(spec, "ptr", 0):
+        return "spec must be a PatchSpec, got None"
+    dims = spec.dims
+    if len(dims) != 4 or dims[0][0] * dims[1][0] * dims[2][0] != T or T < 1:
+        return f"spec shape {tuple(d[0] for d in dims)} does not flatten to T = {T} rows"
+    if dims[3][0] > ld:
+        return f"spec's last dimension {dims[3][0]} is wider than ld = {ld}"
+    for n, runs, _ in dims:
+        if len(runs) > 8 or any(lo < 0 or hi > n or lo > hi for lo, hi in runs):
+            return f"spec ranges {runs} leave [0, {n})"
+    rows = 2 * T if mode == 0 else T
+    if act.numel() == 0 or (rows - 1) * ld + dims[3][0] > _avail(act):
+        return f"act holds {_avail(act)} elements, {rows} rows of pitch {ld} need {(rows - 1) * ld + dims[3][0]}"
+    return None
+
+
+def sparse_pair_f32(act, T: int, ld: int, spec, mode: int) -> None:
+    """:func:`sparse_pair` for an fp32 activation (``iit_sparse_pair_f32``): ``act`` is ``[2T][ld]`` (mode 0: the
+    selected elements of rows ``[T, 2T)`` are copied to rows ``[0, T)`` in place) or ``[T][ld]`` (mode 1: the selected
+    elements are zeroed); ``spec`` is a ``PatchSpec`` whose leading three dimensions flatten to T rows.  Raises
+    ``ValueError`` before any launch for what the kernel does not take."""
+    why = _sparse_pair_f32_why(act, T, ld, spec, mode)
+    if why is not None:
+        raise ValueError(f"sparse_pair_f32: {why}")
+    if CHECK_BOUNDS:
+        _bounds("sparse_pair_f32", ("act", act, 2 * T if mode == 0 else T, int(spec.dims[3][0]), ld))
+    _check(lib().iit_sparse_pair_f32(_p(act), T, ld, spec.ptr, int(mode), _stream()), "sparse_pair_f32")
 
 
 def swiglu_splice_fwd(gate, up, post, src, spec_ptr):

@@ -40,7 +40,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--graphs", type=int, default=1, help="1: engine default, 2: force graphs, 0: eager")
     ap.add_argument("--seed", type=int, default=0, help="torch / numpy seed (the reference uses 0)")
-    ap.add_argument("--fp32-backend", default="torch", choices=["torch", "hip32", "hip32x", "hip32n"],
+    ap.add_argument("--fp32-backend", default="torch", choices=["torch", "hip32", "hip32x", "hip32n", "hip32p"],
                     help="op backend of an fp32 native run, as train_ioi.py --fp32-backend")
     ap.add_argument("--dump-epochs", default=None, help="write every epoch's (epoch, wall s, metrics) as JSON lines")
     args = ap.parse_args()
@@ -61,7 +61,7 @@ def main():
         cfg.update(ioi_cfg)
     cfg.update(init_weights=True, device=str(dev), dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     ll = HookedTransformer(cfg)
-    if args.dtype == "fp32" and args.engine == "native" and args.fp32_backend in ("hip32", "hip32x", "hip32n"):
+    if args.dtype == "fp32" and args.engine == "native" and args.fp32_backend in ("hip32", "hip32x", "hip32n", "hip32p"):
         ll.set_op_backend(args.fp32_backend)
     elif args.dtype == "fp32" or args.engine == "reference":
         ll.set_op_backend("torch")
@@ -142,6 +142,10 @@ def main():
            "final": {k: round(float(v), 3) for k, v in last.items()},
            "device": torch.cuda.get_device_name() if dev.type == "cuda" else "cpu",
            "data": "synthetic (offline IOI prompts, random-init weights)"}
+    calls = getattr(type(ll.ops()), "calls", None)
+    if calls is not None:  # the hip32 family's per-op counters (under graphs: the calls made while capturing)
+        rec["fp32_backend"] = args.fp32_backend
+        rec["backend_calls"] = dict(sorted(calls.items()))
     if pdist.is_main():
         print(json.dumps(rec))
     pdist.destroy()
