@@ -27,7 +27,7 @@
 //   gelu_new_f / gelu_new_grad_f of common.h (the sigmoid form).
 // * Workgroup order: the bijective XCD remap of gemm.hip, so the tiles one XCD works on are consecutive (they share
 //   A row panels in that XCD's L2).  It changes which workgroup computes a tile, never what it computes.
-#include "common.h"
+#include "gemm_f32_body.h"  // F32Tile, the XCD remap, the split-order sum
 
 namespace {
 
@@ -48,76 +48,6 @@ struct F32Args {
   int splits;
   int epi;
 };
-
-template <bool KMAJ, int ROWS, int BK>
-struct F32Tile {
-  static constexpr int PITCH = KMAJ ? ROWS + 16 : BK + 2;
-  static constexpr int ELEMS = KMAJ ? BK * PITCH : ROWS * PITCH;
-  static constexpr int PER_THREAD = ROWS * BK / 4 / 256;  // float4 chunks per thread
-  static_assert(ROWS * BK / 4 % 256 == 0, "tile must split into whole float4 chunks per thread");
-  float4 r[PER_THREAD];
-
-  // chunk c of the tile: 4 consecutive elements along the operand's contiguous dimension
-  static __device__ __forceinline__ void where(int c, int& row, int& k) {
-    if (KMAJ) {
-      k = c / (ROWS / 4);
-      row = (c % (ROWS / 4)) * 4;
-    } else {
-      row = c / (BK / 4);
-      k = (c % (BK / 4)) * 4;
-    }
-  }
-
-  __device__ __forceinline__ void load(const float* base, long ld, int row0, int nrows, int k0, int kend, int tid) {
-#pragma unroll
-    for (int i = 0; i < PER_THREAD; ++i) {
-      int row, k;
-      where(tid + i * 256, row, k);
-      row += row0;
-      k += k0;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row < nrows && k < kend) {
-        const long off = KMAJ ? (long)k * ld + row : (long)row * ld + k;
-        const int n = KMAJ ? nrows - row : kend - k;  // valid elements of this chunk
-        if (n >= 4) {
-          v = *(const float4*)(base + off);
-        } else {
-          v.x = base[off];
-          if (n > 1) v.y = base[off + 1];
-          if (n > 2) v.z = base[off + 2];
-        }
-      }
-      r[i] = v;
-    }
-  }
-
-  __device__ __forceinline__ void store(float* lds, int tid) const {
-#pragma unroll
-    for (int i = 0; i < PER_THREAD; ++i) {
-      int row, k;
-      where(tid + i * 256, row, k);
-      if (KMAJ) {
-        *(float4*)(lds + k * PITCH + row) = r[i];
-      } else {
-        float* d = lds + row * PITCH + k;
-        *(float2*)d = make_float2(r[i].x, r[i].y);
-        *(float2*)(d + 2) = make_float2(r[i].z, r[i].w);
-      }
-    }
-  }
-
-  // 16x16x4 operand fragment: lane l gets X[row0 + (l & 15)][kb + (l >> 4)]
-  static __device__ __forceinline__ float frag(const float* lds, int row0, int kb, int lane) {
-    if (KMAJ) return lds[(kb + (lane >> 4)) * PITCH + row0 + (lane & 15)];
-    return lds[(row0 + (lane & 15)) * PITCH + kb + (lane >> 4)];
-  }
-};
-
-__device__ __forceinline__ int xcd_remap_f32(int bid, int nwg) {
-  const int xcd = bid % 8;
-  const int q = nwg / 8, r = nwg % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-}
 
 __device__ __forceinline__ void epilogue_f32(const F32Args& p, int row, int col, float v) {
   float* dst = p.C + (long)row * p.ldc + col;
@@ -226,9 +156,7 @@ __global__ __launch_bounds__(256) void gemm_f32_reduce_kernel(F32Args p) {
   const long total = (long)p.M * p.N;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
-  float v = p.ws[idx];
-  for (int s = 1; s < p.splits; ++s) v = v + p.ws[s * total + idx];
-  epilogue_f32(p, (int)(idx / p.N), (int)(idx % p.N), v);
+  epilogue_f32(p, (int)(idx / p.N), (int)(idx % p.N), f32_split_sum(p.ws, p.splits, total, idx));
 }
 
 template <int BM, int BN, int BK>
@@ -242,8 +170,6 @@ hipError_t launch_mode(const F32Args& a, int mode, hipStream_t s) {
   }
   return hipGetLastError();
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 

@@ -36,11 +36,17 @@ def parse(argv=None):
     ap.add_argument("--channels-last", type=int, default=1,
                     help="1: NHWC ResNet on the GPU -- MIOpen's NHWC convolutions and the fused NHWC BatchNorm / pool "
                          "kernels (fp32 PVR step 18.9 -> 14.6 ms, profiles/bn_fp32_r5.txt)")
+    ap.add_argument("--fp32-conv", default="torch", choices=["torch", "hip32"],
+                    help="hip32: the fp32 convolutions on the repo's exact-fp32 implicit-GEMM kernels "
+                         "(csrc/conv_f32.hip) instead of MIOpen; opt-in, needs a GPU and --channels-last 1 "
+                         "(measurements: profiles/conv_f32_kernels.txt, profiles/conv_f32_pvr_step.txt)")
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     args = parse(argv)
+    if args.fp32_conv == "hip32" and not (torch.cuda.is_available() and args.channels_last):
+        raise SystemExit("--fp32-conv hip32 needs a GPU and --channels-last 1")
     pdist.init_distributed()
     if torch.cuda.is_available():
         torch.backends.cudnn.benchmark = bool(args.conv_benchmark)
@@ -52,10 +58,15 @@ def main(argv=None):
                                                                 "mode": args.mode, "hook_point": args.hook_point})
     if args.channels_last and torch.cuda.is_available():
         ll_model.to(memory_format=torch.channels_last)  # (state_dict layout-independent: checkpoints interchange)
+    if args.fp32_conv != "torch":  # once the model is channels-last: every convolution from here on is the kernels'
+        from iit_amd.ops import conv_f32
+        conv_f32.set_backend(args.fp32_conv)
     model_pair = IITBehaviorModelPair(ll_model=ll_model, hl_model=hl_model, corr=corr, training_args=training_args)
     model_pair.train(train_set, test_set, epochs=args.epochs, use_wandb=args.wandb)
     if pdist.is_main():
         print("done training")
+        if args.fp32_conv != "torch":  # Python-side calls (a captured step is counted once, at capture)
+            print(f"fp32 convolutions ({args.fp32_conv}): {dict(conv_f32.calls)}")
         if args.save:
             os.makedirs(os.path.dirname(args.save) or ".", exist_ok=True)
             torch.save({k: v.detach().clone() for k, v in ll_model.state_dict().items()}, args.save)

@@ -17,6 +17,7 @@ other inputs take the module path.
 from __future__ import annotations
 
 import os
+import sys
 
 import torch
 from torch import nn
@@ -27,7 +28,8 @@ class Conv2d(nn.Conv2d):
     in a flat parameter arena, convolves with the arena's bf16 mirror (``torch_ops._MirrorWeight``, written by the
     fused Adam): no per-forward weight cast (autocast's weight cache is off in graph-captured steps), and the bf16
     weight gradient is added straight into the fp32 grad slot instead of a cast + AccumulateGrad add.
-    ``IIT_CONV_MIRROR=0`` keeps the plain autocast path."""
+    ``IIT_CONV_MIRROR=0`` keeps the plain autocast path.  Outside autocast, ``ops.conv_f32.set_backend("hip32")``
+    (opt-in, default ``"torch"``) runs the fp32 convolutions it covers on ``csrc/conv_f32.hip``."""
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         w = self.weight
@@ -42,6 +44,11 @@ class Conv2d(nn.Conv2d):
                     return hconv.conv(x, w, m[0], hconv.geometry(self))
                 w16 = _MirrorWeight.apply(w, m[0]) if torch.is_grad_enabled() else m[1]
                 return self._conv_forward(x.to(torch.bfloat16), w16, None)
+        # opt-in fp32 implicit-GEMM kernels (csrc/conv_f32.hip): only once someone has imported ops.conv_f32 and
+        # called set_backend("hip32"); this module never imports it
+        cf = sys.modules.get("iit_amd.ops.conv_f32")
+        if cf is not None and cf.backend() == "hip32" and not torch.is_autocast_enabled("cuda") and cf.covered(x, self):
+            return cf.conv(x, self)
         return super().forward(x)
 
 

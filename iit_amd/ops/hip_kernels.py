@@ -36,6 +36,11 @@ _SIGS = {
     "iit_gemm_f32_ok": [c_void_p] * 6 + [c_long] * 4 + [c_int] * 7,
     "iit_gemm_f32_aux": [c_void_p] * 7 + [c_long] * 5 + [c_int] * 7 + [c_void_p],
     "iit_gemm_f32_aux_ok": [c_void_p] * 7 + [c_long] * 5 + [c_int] * 7,
+    "iit_conv_f32_ok": [c_int] + [c_void_p] * 4 + [c_int] * 12,
+    "iit_conv_f32_plan": [c_int] * 13 + [c_void_p],
+    "iit_conv_f32_fwd": [c_void_p] * 4 + [c_int] * 12 + [c_void_p],
+    "iit_conv_f32_dgrad": [c_void_p] * 4 + [c_int] * 12 + [c_void_p],
+    "iit_conv_f32_wgrad": [c_void_p] * 4 + [c_int] * 12 + [c_void_p],
     "iit_ln_f32_part_rows": [],
     "iit_ln_f32_fwd_ok": [c_void_p] * 6 + [c_int, c_int, c_long, c_long],
     "iit_ln_f32_fwd": [c_void_p] * 6 + [c_int, c_int, c_long, c_long, c_float, c_void_p],
@@ -474,6 +479,73 @@ def gemm_f32(A, B, C, *, M, N, K, lda, ldb, ldc, mode, epi, bias=None, resid=Non
     ws = torch.empty(splits * M * N, dtype=torch.float32, device=A.device) if splits > 1 else None
     _check(lib().iit_gemm_f32_aux(_p(A), _p(B), _p(C), _p(bias), _p(resid), _p(aux), _p(ws), lda, ldb, ldc, ldr, ldx,
                                   M, N, K, mode, epi, tile, splits, _stream()), "iit_gemm_f32")
+
+
+# ------------------------------------------------------------------------------ exact-fp32 convolutions (csrc/conv_f32.hip)
+CONV_F32_FWD, CONV_F32_DGRAD, CONV_F32_WGRAD = 0, 1, 2
+CONV_F32_PLAN_FIELDS = ("M", "N", "K", "k_per_split", "grid_x", "vector")
+
+
+def conv_f32_geom(N, H, W, Cin, Cout, k, s, pad):
+    """The geometry tuple the fp32 convolution calls take: ``(N, H, W, Cin, OH, OW, Cout, k, s, pad)``."""
+    return (N, H, W, Cin, (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1, Cout, k, s, pad)
+
+
+def conv_f32_plan(pass_: int, geom, tile: int = 0, splits: int = 1):
+    """The library's own arithmetic for one pass (pure host): dict of ``CONV_F32_PLAN_FIELDS`` -- the GEMM extents,
+    the K range of a split, the workgroups per split and whether the geometry allows float4 gathers -- or None for a
+    geometry it refuses."""
+    out = (c_int * 6)()
+    if lib().iit_conv_f32_plan(pass_, *geom, tile, splits, ctypes.cast(out, c_void_p)) != 0:
+        return None
+    return dict(zip(CONV_F32_PLAN_FIELDS, list(out)))
+
+
+def conv_f32_ok(pass_: int, x, w, y, geom, tile: int = 0, splits: int = 1) -> bool:
+    """Whether the fp32 convolution kernels cover this problem: fp32 GPU tensors (``x``, ``w``, ``y``: the tensors of
+    those shapes, whichever the pass writes), a geometry ``csrc/conv_f32.hip`` lists, tile 0 / 1, 1..64 splits."""
+    if not _f32_cuda(x, w, y) or x is None or w is None or y is None:
+        return False
+    ws = 16 if splits > 1 else None  # the workspace comes from torch's allocator: a stand-in aligned address
+    return bool(lib().iit_conv_f32_ok(pass_, _p(x), _p(w), _p(y), ws, *geom, tile, splits))
+
+
+def _conv_f32(pass_, name, x, w, y, geom, tile, splits):
+    if not conv_f32_ok(pass_, x, w, y, geom, tile, splits):
+        raise RuntimeError(f"{name}: unsupported problem (N, H, W, Cin, OH, OW, Cout, k, s, pad)={tuple(geom)} "
+                           f"tile={tile} splits={splits} (dense NHWC fp32 GPU tensors, 1 <= k <= 7, stride 1 or 2, "
+                           f"0 <= pad < k)")
+    N, H, W, Cin, OH, OW, Cout, k, s, pad = geom
+    if CHECK_BOUNDS:
+        _bounds(name, ("x", x, 1, N * H * W * Cin, 0), ("w", w, 1, Cout * k * k * Cin, 0),
+                ("y", y, 1, N * OH * OW * Cout, 0))
+    ws = None
+    if splits > 1:
+        pl = conv_f32_plan(pass_, geom, tile, splits)
+        ws = torch.empty(splits * pl["M"] * pl["N"], dtype=torch.float32, device=x.device)
+    fn = getattr(lib(), name)
+    a, b, out = ((x, w, y), (y, w, x), (x, y, w))[pass_]
+    _check(fn(_p(a), _p(b), _p(out), _p(ws), *geom, tile, splits, _stream()), name)
+
+
+def conv_f32_fwd(x, w, y, geom, tile: int = 0, splits: int = 1):
+    """``y [N][OH][OW][Cout] = conv(x [N][H][W][Cin], w [Cout][k][k][Cin])`` in exact fp32 (``csrc/conv_f32.hip``):
+    the tensors' storage from their first element on is read as those dense arrays.  ``splits > 1``: deterministic
+    split-K through a workspace allocated here with ``torch.empty`` (capture-safe, like ``gemm_f32``'s).  Raises,
+    without launching, for a problem ``conv_f32_ok`` refuses."""
+    _conv_f32(CONV_F32_FWD, "iit_conv_f32_fwd", x, w, y, geom, tile, splits)
+
+
+def conv_f32_dgrad(dy, w, dx, geom, tile: int = 0, splits: int = 1):
+    """``dx [N][H][W][Cin]`` of the convolution from ``dy [N][OH][OW][Cout]`` and the forward weight in place; every
+    element of ``dx`` is written.  Otherwise as :func:`conv_f32_fwd`."""
+    _conv_f32(CONV_F32_DGRAD, "iit_conv_f32_dgrad", dx, w, dy, geom, tile, splits)
+
+
+def conv_f32_wgrad(x, dy, dw, geom, tile: int = 0, splits: int = 1):
+    """``dw [Cout][k][k][Cin]`` of the convolution, reduced over the output pixels in ascending order.  Otherwise as
+    :func:`conv_f32_fwd`."""
+    _conv_f32(CONV_F32_WGRAD, "iit_conv_f32_wgrad", x, dw, dy, geom, tile, splits)
 
 
 # ------------------------------------------------------------------------------ fp32 block glue (csrc/block_f32.hip)

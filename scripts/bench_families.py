@@ -43,6 +43,8 @@ def parse(argv=None):
                     help="pvr-resnet18 only: fp32 (the reference precision) or channels-last bf16 autocast")
     ap.add_argument("--channels-last", type=int, default=None,
                     help="pvr-resnet18: NHWC model and activations (default on)")
+    ap.add_argument("--fp32-conv", choices=["torch", "hip32"], default="torch",
+                    help="pvr-resnet18, fp32: hip32 = the convolutions on csrc/conv_f32.hip (train.py --fp32-conv)")
     ap.add_argument("--graphs", type=int, default=None,
                     help="HIP-graph phases (default: on for BERT; off for Llama, whose strict phase has one graph per "
                          "non-circuit node -- ~1000 at 32 layers x 32 heads -- and whose GEMMs are not launch-bound)")
@@ -73,6 +75,9 @@ def setup(args, dev):
         # profiles/pvr_step_r5.txt); IIT_CONV_BENCHMARK=0 keeps MIOpen's immediate-mode heuristic
         torch.backends.cudnn.benchmark = os.environ.get("IIT_CONV_BENCHMARK", "1") == "1"
         from iit_amd.tasks.task_loader import get_alignment, get_dataset
+        if args.fp32_conv != "torch":
+            from iit_amd.ops import conv_f32
+            conv_f32.set_backend(args.fp32_conv)
         n = 20000
         tr_set, te_set = get_dataset("mnist_pvr", {"train_size": n, "test_size": 2048, "device": dev})
         ll, hl, corr = get_alignment("mnist_pvr", {"input_shape": te_set.base_data.get_input_shape(), "device": dev})
